@@ -10,11 +10,21 @@ whole batch + the DDIM pose update.  Every rank holds its own batch of ``--puzzl
 across GPUs with NO data-path collective (weak scaling).  Inputs (piece features, x_T; weights = the
 module's seeded default init) are synthetic and resident in HBM before the timed region; the per-Batch staging
 (``da_denoiser_set_features``: feature copy + the loop-invariant share of mlp.0) happens once per sampling
-loop, OUTSIDE the timed region, and is reported as ``set_features_ms``.  The K timed steps are consecutive iterations
+loop, OUTSIDE the timed region (``set_features_ms`` with --full).  The K timed steps are consecutive iterations
 of the DDIM loop, replayed as hipGraph launches; timing is barrier + synchronize on both sides, MAX over ranks.
-The K-step region is measured 1 + ``--replays`` (30) times, each pass a full contract measurement; ``value`` /
-``ms_per_step`` are the MEDIAN pass, the first pass is kept as ``first_replay`` (one K-step pass is a 10-80 ms sample).
+The K-step region is measured 1 + ``--replays`` times (default 0 extra passes, 30 with --full), each pass a full
+contract measurement; ``value`` / ``ms_per_step`` are the MEDIAN pass, the first pass is kept as ``first_replay``.
 ``--gpus N`` without a launcher around it starts its own N ranks (``self_launch``), like the reference's Trainer.
+
+A plain run (no --full) of a sampling configuration sets up, warms up, times its K steps, writes the outputs asked for
+with --dump-outputs and prints its line; nothing else.  --full adds the side measurements of the line (they take passes
+of their own): the replays above, set_features_ms / graph_plan_ms / fragment_encoder_ms, two Batches in flight, the
+fp32 parity-mode replay, the roofline (+ sparse_path) and the CPU baseline.  The other modes (--config 5 / scripted /
+csr, --mode encode / e2e) measure what they always did, with or without --full.
+
+--dump-outputs DIR: after the timed steps, the poses the timed loop returned in its last step (``x_final`` [N, c],
+float32; rank r > 0: ``x_final_rank<r>``) go to DIR/<name>.npy, at most 64 MB in all (a fixed, seeded row sample of
+anything larger).  Inputs and weights are seeded: the same arguments give the same inputs in every run.
 
 Every BASELINE configuration is driver-runnable with the same JSON schema:
 
@@ -25,12 +35,12 @@ Every BASELINE configuration is driver-runnable with the same JSON schema:
   --config 4    3D fragments: P=20, D=832, SE(3) head, T=300 / ratio 10, bf16, G=256
   --config 5    training: 12x12 rot dense, 64 puzzles per GPU, Huber, Adafactor, one optimizer step per "step"
 
-roofline: per-kernel-class time is measured live with HIP events on the launch stream (da_profile_*), in a separate
+roofline (--full): per-kernel-class time is measured live with HIP events on the launch stream (da_profile_*), in a separate
 eager pass over the same steps.  ``roofline.kernel`` is the class with the LARGEST share of the step's kernel time;
 every class is listed under ``roofline.classes`` with its algorithmic FLOP (the reference's formulation) and
 the FLOP / bytes the kernels really execute after the algebraic folds of DESIGN 3c; ``attention_total`` is the
 north-star figure (MFMA utilisation of the dense attention, all four layers).
-cpu_baseline: the CPU oracle (pure-torch fp32 restatement of the reference, oracle/) timed on this box's host cores on
+cpu_baseline (--full): the CPU oracle (pure-torch fp32 restatement of the reference, oracle/) timed on this box's host cores on
 ONE puzzle: thread count chosen by a sweep, 1 warm-up + 3 repeats, median -- baseline only.
 """
 import argparse
@@ -783,9 +793,9 @@ def sample_bench(args, world, rank, dev):
     K, Wm = args.steps, args.warmup
     n = cfg["n"]
     threed = cfg["variant"] == "3d"
+    full = args.full
     model = build_module(cfg, dev, prec)
     eng = model.model.engine(dev)
-    sd = {k: v.detach().cpu() for k, v in model.model._denoiser_state().items()}        # for the CPU baseline leg
     gen = torch.Generator(device=dev).manual_seed(1234 + rank)
     N = G * n
     feats = torch.randn((N, 768 if threed else 1088), generator=gen, device=dev)
@@ -804,10 +814,12 @@ def sample_bench(args, world, rank, dev):
         make_plan = lambda: eng.plan(ei, batch)  # noqa: E731
     plan = make_plan()                           # (first call: torch's lazy initialisation of its index kernels)
     torch.cuda.synchronize()
-    tp0 = time.perf_counter()
-    plan = make_plan()
-    torch.cuda.synchronize()
-    plan_ms = (time.perf_counter() - tp0) * 1e3
+    plan_ms = None
+    if full:
+        tp0 = time.perf_counter()
+        plan = make_plan()
+        torch.cuda.synchronize()
+        plan_ms = (time.perf_counter() - tp0) * 1e3
     E = int(plan.n_edges)
     sch = model._schedule()
     mt = _lib.MEAN_START_X if cfg["mean"] == "START_X" else _lib.MEAN_EPSILON
@@ -820,14 +832,15 @@ def sample_bench(args, world, rank, dev):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     eng.set_features(plan, feats)
     torch.cuda.synchronize()
-    e0.record()
-    for _ in range(3):
-        eng.set_features(plan, feats)
-    e1.record()
-    torch.cuda.synchronize()
-    set_features_ms = e0.elapsed_time(e1) / 3
-    fragment_encoder_ms = None
-    if threed:
+    set_features_ms = fragment_encoder_ms = None
+    if full:
+        e0.record()
+        for _ in range(3):
+            eng.set_features(plan, feats)
+        e1.record()
+        torch.cuda.synchronize()
+        set_features_ms = e0.elapsed_time(e1) / 3
+    if full and threed:
         # once per sampling loop too (...double_diffusion.py:700): the G x 20 fragments of 1 000 points through the VN-DGCNN
         pts = synthetic_fragments(N, 1000, dev, 5 + rank)
         model.model.pcd_features(pts)
@@ -867,6 +880,8 @@ def sample_bench(args, world, rank, dev):
     for _ in range(1 + max(args.replays, 0)):
         dt_i, x_final = timed_pass()
         local.append(dt_i)
+    if args.dump_outputs:           # (x_final is an engine-owned buffer: written before any other loop of this shape runs)
+        dump_outputs(args.dump_outputs, {"x_final" + (f"_rank{rank}" if rank else ""): x_final})
     per_rank = [local]
     if world > 1:
         import torch.distributed as dist
@@ -887,7 +902,7 @@ def sample_bench(args, world, rank, dev):
     # Batches that cannot be SPLIT into two branches (exophormer: the virtual-node edges couple a Batch's puzzles) get the two-stream
     # overlap with TWO independent Batches in flight (DenoiserEngine.sample_loop_batches; each Batch bit for bit what it computes alone)
     in_flight = None
-    if plan.hybrid and not eng._two_branch(plan, False, True) and _lib.config().pair_split:
+    if full and plan.hybrid and not eng._two_branch(plan, False, True) and _lib.config().pair_split:
         perms2 = expander_perms(cfg, G, 103 + rank).to(dev)
         plan2 = eng.plan_expander(perms2, args.degree)
         gen2 = torch.Generator(device=dev).manual_seed(4321 + rank)
@@ -921,7 +936,7 @@ def sample_bench(args, world, rank, dev):
 
     roof = sparse = None
     flags = int(eng.flags)
-    if not args.no_roofline:
+    if full and not args.no_roofline:
         kp = min(K, 20, its)
         tf = os.path.join(ROOT, "profiles", PROFILE_ROUND, "pmc_traffic.json")
         pmc_key = args.config + (f"_d{args.degree}" if cfg["graph"] == "regular" else "")
@@ -993,7 +1008,7 @@ def sample_bench(args, world, rank, dev):
     del ei
 
     parity = None
-    if prec == "bf16" and not args.no_parity_mode:
+    if full and prec == "bf16" and not args.no_parity_mode:
         # the mode whose parity bound is north_star's 1e-4 (fp32 storage, exact-fp32 MFMA): same Batch, same loop, one
         # captured replay of min(K, 20) steps after one untimed replay -- reported beside the benched bf16 figure
         model.model.precision = "fp32"
@@ -1025,7 +1040,8 @@ def sample_bench(args, world, rank, dev):
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
+            sd = {k: v.detach().cpu() for k, v in model.model._denoiser_state().items()}
             cpu = cpu_baseline(cfg, sd, args.degree, args.cpu_baseline_full)
         value = world * G * K / dt
         f_node = 6_164_704 if threed else F_NODE
@@ -1037,7 +1053,8 @@ def sample_bench(args, world, rank, dev):
             "value": value, "unit": "puzzle-steps/s", "n_gpus": world, "steps": K, "warmup": Wm,
             "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": prec, "data": "synthetic",
-            "value_is": f"median of {len(passes)} timed K-step passes (each: barrier + synchronize both sides, MAX over ranks)",
+            "value_is": (f"median of {len(passes)} timed K-step passes" if len(passes) > 1 else "one timed K-step pass")
+                        + " (each: barrier + synchronize both sides, MAX over ranks)",
             "first_replay": {"value": world * G * K / dt_first, "ms_per_step": dt_first / K * 1e3},
             "distributed": dist_info(world, rank_ms),
             "config": {"workload": wl, "baseline_config": args.config, "puzzles_per_gpu": G, "global_puzzles": world * G,
@@ -1306,6 +1323,23 @@ def dist_info(world, rank_ms=None):
     return {"world_size": dist.get_world_size(), "backend": dist.get_backend(), "per_rank_ms_per_step": rank_ms}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor) as out_dir/<name>.npy in float32.  Over 64 MB in all, every array keeps
+    the same fixed, seeded sample of its rows (sorted), so that two builds are compared row for row."""
+    import numpy as np
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in host.items():
+        if total > DUMP_LIMIT_BYTES and v.ndim and v.shape[0] > 1:
+            keep = max(1, int(v.shape[0] * DUMP_LIMIT_BYTES / total))
+            v = v[np.sort(np.random.default_rng(0).choice(v.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
+
+
 def gather_rank_times(seconds, dev):
     """Every rank's own wall time of the timed region -> list on every rank (the job time is the max)."""
     import torch.distributed as dist
@@ -1344,7 +1378,13 @@ def main():
     ap.add_argument("--pixels", action="store_true",
                     help="--mode train: train the piece encoder too, from 32x32 crops (the scripted --backbone resnet18equiv)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="gloo: ranks may share a GPU (functional check of the N > 1 path on a 1-GPU box)")
-    ap.add_argument("--replays", type=int, default=30, help="extra individually timed graph replays for the median")
+    ap.add_argument("--replays", type=int, default=None,
+                    help="extra individually timed graph replays for the median (default: 30; 0 in a sampling run without --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="sampling configurations: also the side measurements (replays, staging / plan times, two Batches in flight, "
+                         "fp32 parity mode, roofline, CPU baseline); without it a run times its K steps and nothing else")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="sampling configurations: write the timed loop's last output (x_final) to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="also time the oracle with ONE thread at full size")
     ap.add_argument("--no-roofline", action="store_true")
@@ -1356,6 +1396,13 @@ def main():
     args.degree_given = any(a == "--degree" or a.startswith("--degree=") for a in sys.argv[1:])
     if args.config == "5":
         args.mode = "train"
+    sampling = args.mode == "sample" and args.config not in ("scripted", "csr")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and not sampling:
+        ap.error("--dump-outputs: the sampling configurations (--config 1 / 2 / 3 / 3p / 4) only")
+    if args.replays is None:
+        args.replays = 0 if (sampling and not args.full) else 30
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)

@@ -41,6 +41,41 @@ def test_bench_gpus_2_self_launches_training():
     assert line["config"]["global_puzzles"] == 8 and line["value"] > 0
 
 
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_final_poses(tmp_path):
+    """Without --full a run times exactly its K steps once and measures nothing else; --dump-outputs writes the poses of the
+    timed loop's last step."""
+    import numpy as np
+    line = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--puzzles", "2", "--dump-outputs", str(tmp_path))
+    assert line["steps"] == 3 and line["replay"]["passes"] == 1 and line["replay"]["steps_per_pass"] == 3
+    assert abs(line["value"] - 2 * 3 / (line["ms_per_step"] * 3e-3)) / line["value"] < 1e-6
+    assert line["roofline"] is None and line["parity_mode"] is None and line["cpu_baseline"] is None
+    x = np.load(tmp_path / "x_final.npy")
+    assert x.dtype == np.float32 and x.shape == (2 * 900, 4) and np.isfinite(x).all()
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_row_sample_over_the_cap(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    bench.dump_outputs(str(tmp_path / "a"), {"x": torch.arange(12.).reshape(6, 2).half(), "y": torch.ones(3)})
+    x, y = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "y.npy")
+    assert x.dtype == np.float32 and x.shape == (6, 2) and (x.ravel() == np.arange(12)).all() and (y == 1).all()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 256)
+    big = torch.arange(400.).reshape(200, 2)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"x": big})
+    b, c = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert 0 < b.nbytes <= 256 and b.shape[1] == 2 and np.array_equal(b, c)           # same rows in every run
+    assert (np.diff(b[:, 0]) > 0).all() and (b[:, 1] == b[:, 0] + 1).all()              # whole rows, in order
+
+
+def test_bench_rejects_arguments_it_cannot_honour():
+    for argv, msg in ((["--steps", "0"], "--steps must be at least 1"), (["--config", "5", "--dump-outputs", "d"], "--dump-outputs")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True, cwd=ROOT, timeout=300)
+        assert r.returncode == 2 and msg in r.stderr, r.stderr[-2000:]
+
+
 def test_bench_gpus_n_without_enough_gpus_says_so():
     """No GPU (this container) or fewer than N: a clear message, not an assertion about WORLD_SIZE."""
     import torch

@@ -28,6 +28,19 @@ def stats(t):
     return torch.stack([t.sum(), t.abs().sum(), (t * t).sum()]).float()
 
 
+def assert_grad_matches(fixture, case, k, grad):
+    """A parameter's gradient against the reference's (first 64 entries + digests, 1e-3).  d loss / d lin_key.bias is 0 in exact
+    arithmetic (the bias shifts every score of a query by the same q . b, and softmax ignores a shift): both values are rounding
+    noise whose digits follow the machine's summation order (vector width, thread count), so both are held to the noise level."""
+    head = fixture[f"{case}/grad_head/{k}"]
+    if k.endswith("lin_key.bias"):
+        scale = max(float(np.abs(fixture[f]).max()) for f in fixture.files if f.startswith(f"{case}/grad_head/"))
+        assert max(float(grad.abs().max()), float(np.abs(head).max())) < 1e-7 * scale, k
+        return
+    assert rel_err(grad.flatten()[:64], head) < 1e-3, k
+    assert rel_err(stats(grad), fixture[f"{case}/grad_stats/{k}"]) < 1e-3, k
+
+
 # ------------------------------------------------------------------ PyG boundary (unpinned)
 @pytest.mark.parametrize("n,H,C", [(36, 8, 32), (50, 8, 144)])
 def test_transformer_conv_equals_sdpa_on_complete_graph(n, H, C):
@@ -139,12 +152,25 @@ def test_so3_scale_is_matrix_power():
 
 
 # ------------------------------------------------------------------ schedules (a-1)
+# Buffers whose last op is torch's fp32 sqrt, as the reference computes them (spatial_diffusion.py:292-312) from buffers the
+# fixture holds too.  torch's CPU sqrt rounds differently on different processors (by 1 ulp at most), so the fixture holds the
+# bits of the machine that wrote it: these are compared bit for bit with the reference's own expression on this machine.
+TORCH_SQRT = {"sqrt_recip_alphas": lambda b: torch.sqrt(1.0 / b["alphas"]),
+              "sqrt_alphas_cumprod": lambda b: torch.sqrt(b["alphas_cumprod"]),
+              "sqrt_one_minus_alphas_cumprod": lambda b: torch.sqrt(1.0 - b["alphas_cumprod"])}
+
+
 @pytest.mark.parametrize("T", C.SCHEDULE_T)
 def test_schedule_buffers_bit_exact(golden, T):
     sch = DF.make_schedule(T)
+    ref = {k: torch.from_numpy(golden[f"schedule_T{T}/{k}"]) for k in sch}
     for k, v in sch.items():
-        ref = golden[f"schedule_T{T}/{k}"]
-        assert np.array_equal(v.numpy(), ref), k
+        want = ref[k]
+        if k in TORCH_SQRT:
+            here = TORCH_SQRT[k](ref)
+            assert int((here.view(torch.int32) - want.view(torch.int32)).abs().max()) <= 1, k
+            want = here
+        assert torch.equal(v, want), k
 
 
 # ------------------------------------------------------------------ 2D forward (a-3..a-8)
@@ -266,8 +292,7 @@ def test_p_losses_and_gradients_match_reference(golden, tr):
     for k, p in sd.items():
         key = f"{tr['name']}/grad_head/{k}"
         if key in golden.files:
-            assert rel_err(p.grad.flatten()[:64], golden[key]) < 1e-3, k
-            assert rel_err(stats(p.grad), golden[f"{tr['name']}/grad_stats/{k}"]) < 1e-3, k
+            assert_grad_matches(golden, tr["name"], k, p.grad)
             n += 1
     assert n >= 28
 
@@ -292,8 +317,7 @@ def test_exophormer_p_losses_and_gradients_match_reference(tr):
     for k, p in sd.items():
         key = f"{tr['name']}/grad_head/{k}"
         if key in g4.files:
-            assert rel_err(p.grad.flatten()[:64], g4[key]) < 1e-3, k
-            assert rel_err(stats(p.grad), g4[f"{tr['name']}/grad_stats/{k}"]) < 1e-3, k
+            assert_grad_matches(g4, tr["name"], k, p.grad)
             n += 1
     assert n == 46
 

@@ -17,7 +17,7 @@ cd /tmp
 # loop launches every kernel twice at half size and, under --kernel-trace, runs the branches serially (tools/graph_idle_probe.py).
 # profiles/r03/r03_rocprof_kernel_stats_headline_two_branch.txt is the same collection with the default loop.
 export DA_TWO_BRANCH=${DA_TWO_BRANCH:-0}
-BENCH="python $REPO/bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-parity-mode --replays 0 $*"
+BENCH="python $REPO/bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-parity-mode --replays 0 $*"
 timeout 600 rocprofv3 --kernel-trace --stats -d $W/stats -o s -- $BENCH > $W/stats.log 2>&1
 DB=$(find $W/stats -name "*results.db" | head -1)
 python $REPO/profiles/rocpd_stats.py $DB > $OUT/${ROUND}_rocprof_kernel_stats_$TAG.txt 2>&1

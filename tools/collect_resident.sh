@@ -12,5 +12,5 @@ bash tools/collect_attn_pmc.sh > /dev/null 2>&1
 cp $O/${ROUND}_pmc_*.txt $O/${ROUND}_rocprof_*.txt profiles/$ROUND/ 2>/dev/null
 python tools/make_pmc_json.py $ROUND > $O/${ROUND}_make_pmc_json.log 2>&1
 cp profiles/$ROUND/pmc_traffic.json profiles/$ROUND/pmc_attention_sq.json $O/ 2>/dev/null
-timeout 900 python bench.py --steps 100 --warmup 10 > $O/${ROUND}_bench_config_3p.json 2> $O/${ROUND}_bench_config_3p.err
+timeout 900 python bench.py --full --steps 100 --warmup 10 > $O/${ROUND}_bench_config_3p.json 2> $O/${ROUND}_bench_config_3p.err
 tail -c 600 $O/${ROUND}_bench_config_3p.json

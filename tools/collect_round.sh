@@ -26,7 +26,7 @@ mkdir -p profiles/$ROUND
 cp $O/${ROUND}_pmc_*.txt $O/${ROUND}_rocprof_*.txt profiles/$ROUND/ 2>/dev/null
 python tools/make_pmc_json.py $ROUND > $O/${ROUND}_make_pmc_json.log 2>&1
 cp profiles/$ROUND/pmc_traffic.json profiles/$ROUND/pmc_attention_sq.json $O/ 2>/dev/null
-b() { tag=$1; shift; timeout 900 python bench.py "$@" > $O/${ROUND}_bench_$tag.json 2> $O/${ROUND}_bench_$tag.err; tail -c 300 $O/${ROUND}_bench_$tag.json | head -c 0; echo "bench $tag rc=$?"; }
+b() { tag=$1; shift; timeout 900 python bench.py --full "$@" > $O/${ROUND}_bench_$tag.json 2> $O/${ROUND}_bench_$tag.err; tail -c 300 $O/${ROUND}_bench_$tag.json | head -c 0; echo "bench $tag rc=$?"; }
 b config_3p --steps 100 --warmup 10
 b config_1 --config 1
 b config_2 --config 2
