@@ -99,6 +99,28 @@ class DaPcdEncoderWeights(C.Structure):
     ]
 
 
+PCD_TRAIN_LAYERS = 8      # conv1..conv6, VnInv.vn1, VnInv.vn2
+
+
+class DaPcdTrainWeights(C.Structure):
+    _fields_ = [
+        ("feat_dim", C.c_int32), ("reserved0", C.c_int32),
+        ("premap", _fp * PCD_STAGES), ("bn_a", _fp * PCD_STAGES), ("conv_b", _fp * PCD_STAGES),
+        ("conv6", _fp), ("linear0", _fp),
+        ("gamma", _fp * PCD_TRAIN_LAYERS), ("beta", _fp * PCD_TRAIN_LAYERS),
+        ("running_mean", _fp * PCD_TRAIN_LAYERS), ("running_var", _fp * PCD_TRAIN_LAYERS),
+        ("momentum", C.c_float * PCD_TRAIN_LAYERS), ("eps", C.c_float * PCD_TRAIN_LAYERS),
+        ("inv_wf", _fp * 2), ("inv_wd", _fp * 2),
+    ]
+
+
+class DaPcdTrainGrads(C.Structure):
+    _fields_ = [
+        ("wf", _fp * 6), ("wd", _fp * 6), ("gamma", _fp * 6), ("beta", _fp * 6),
+        ("linear0_w", _fp), ("linear0_b", _fp), ("points", _fp),
+    ]
+
+
 class DaConfig(C.Structure):
     """include/diffassemble_hip.h `da_config`: the library's switches (one environment variable each, settable at run time)."""
     _fields_ = [(n, C.c_int32) for n in ("struct_bytes", "disable_mfma", "disable_dense", "disable_folds", "attn_level", "xpanel", "tail_next",
@@ -170,6 +192,12 @@ PROTOTYPES = {
     "da_pcd_encoder_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "da_pcd_encoder_forward": (C.c_int, [C.POINTER(DaPcdEncoderWeights), C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp,
                                          C.c_size_t, C.c_int, _fp]),
+    "da_pcd_train_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "da_pcd_train_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "da_pcd_train_forward": (C.c_int, [C.POINTER(DaPcdTrainWeights), C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp,
+                                       C.c_size_t, _fp, C.c_size_t, _fp]),
+    "da_pcd_train_backward": (C.c_int, [C.POINTER(DaPcdTrainWeights), C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp,
+                                        C.POINTER(DaPcdTrainGrads), _fp, C.c_size_t, C.c_int, _fp]),
     "da_knn": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp]),
     "da_nearest_sq": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
     "da_enc_train_scratch_bytes": (C.c_size_t, [C.c_int]),

@@ -219,6 +219,15 @@ int launch_conv_fused(int prec, int heads, int C, int kin, int n_graphs, int max
                       int nodiag, const void *x, int ldx, const void *W, const float *bias, int act, void *out, int ldo,
                       hipStream_t st);
 
+// da_pcd_encoder.hip: the eval passes of the point-cloud encoder, reused by its training path (da_pcd_train.hip)
+int pcd_knn_launch(int clouds, int N, int dim, const float *x, int ldx, int32_t *idx, const float *xn, hipStream_t st);
+int pcd_premap_launch(int C, const float *X, int ldx, const float *Wm, long long total, float *T, hipStream_t st);
+int pcd_edge_launch(const float *T, const int32_t *idx, const float *bn_a, const float *wb, int N, int clouds, float *Xout,
+                    float *xn, hipStream_t st);
+// conv6 + its activation + mean over points (partial: clouds * ceil(N / 256) * feat * 3 floats), then k_pcd_final into out
+int pcd_conv6_final_launch(const float *X1, const float *X2, const float *X3, const float *w6, int feat, int N, int clouds,
+                           float *partial, const float *lin0, int inv, float *out, int ldo, hipStream_t st);
+
 // generic linear dispatch (MFMA when the shape allows, else simple)
 int linear(int prec, int M, int K, int Nout, const void *A, int lda, const void *W, const float *bias, int act,
            const void *res, void *out, int ldo, hipStream_t st);

@@ -688,6 +688,36 @@ static PcdSide *pcd_side() {
     return &c;
 }
 
+// The eval kernels as building blocks of the training path (da_pcd_train.hip): there the BatchNorm scale / shift slots of the
+// packed blobs hold the batch statistics of the call, so the pooling passes are the eval passes unchanged.
+int pcd_knn_launch(int clouds, int N, int dim, const float *x, int ldx, int32_t *idx, const float *xn, hipStream_t st) {
+    return knn_launch(clouds, N, dim, x, ldx, KNN, 0, idx, st, xn);
+}
+int pcd_premap_launch(int C, const float *X, int ldx, const float *Wm, long long total, float *T, hipStream_t st) {
+    const int nb = (int)((total + 255) / 256);
+    if (C == 1) k_pcd_premap<1><<<nb, 256, 0, st>>>(X, ldx, Wm, total, T);
+    else k_pcd_premap<VC><<<nb, 256, 0, st>>>(X, ldx, Wm, total, T);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int pcd_edge_launch(const float *T, const int32_t *idx, const float *bn_a, const float *wb, int N, int clouds, float *Xout,
+                    float *xn, hipStream_t st) {
+    const int ne = ((clouds + 7) / 8) * 8 * ((N + 127) / 128);
+    if (wb) k_pcd_edge<true><<<ne, 128, 0, st>>>(T, idx, bn_a, wb, N, clouds, Xout, xn);
+    else k_pcd_edge<false><<<ne, 128, 0, st>>>(T, idx, bn_a, nullptr, N, clouds, Xout, xn);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int pcd_conv6_final_launch(const float *X1, const float *X2, const float *X3, const float *w6, int feat, int N, int clouds,
+                           float *partial, const float *lin0, int inv, float *out, int ldo, hipStream_t st) {
+    const int nblk = (N + 255) / 256;
+    k_pcd_conv6<<<dim3(nblk, clouds), 256, 0, st>>>(X1, X2, X3, w6, feat, N, partial);
+    DA_LAUNCH_CHECK();
+    k_pcd_final<<<clouds, 256, 0, st>>>(partial, nblk, feat, N, lin0, inv, out, ldo);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace da
 
 using namespace da;

@@ -64,4 +64,14 @@ class Eff_GAT_3d(DenoiserBase):
         if self.pcd_backbone is None:
             raise NotImplementedError(
                 "only the VN-DGCNN point-cloud encoders are built (backbone='vn_dgcnn' / 'vn_dgcnn_inv'): pass pcd_feats")
+        if self.freeze_backbone:
+            # no gradient, but the backbone keeps its mode: in train() its BatchNorms still use and update batch statistics
+            with torch.no_grad():
+                return self.pcd_backbone(pcd)
+        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.pcd_backbone.parameters()):
+            # a trainable backbone only makes sense with the 3D model's own training (p_losses, the 3D denoiser backward),
+            # which is not built: the encoder trains on its own through VN_DGCNN (differentiable in train()), or frozen here
+            raise NotImplementedError(
+                "training Eff_GAT_3d end to end (the 3D denoiser backward and p_losses) is not built: set freeze_backbone=True, "
+                "run pcd_features under torch.no_grad(), or train the VN_DGCNN backbone directly with your own loss")
         return self.pcd_backbone(pcd)

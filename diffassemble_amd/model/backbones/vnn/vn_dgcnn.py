@@ -3,12 +3,17 @@ vn_layers.py): ``VN_DGCNN(feat_dim, inv)`` with the same state-dict keys (``conv
 ``convL.batchnorm.bn.{weight,bias,running_mean,running_var,num_batches_tracked}``, ``convL.map_to_dir.weight``,
 ``VnInv.vn{1,2}.*``, ``VnInv.vn_lin.weight``, ``linear0.{weight,bias}``), so checkpoints load unchanged.
 
-The modules only HOLD parameters; an eval-mode forward runs in libdiffassemble_hip.so through
-``diffassemble_amd.pcd_encoder.PcdEncoderEngine`` (kNN, vector-neuron layers and pooling as HIP kernels; no torch
-fallback).  Training-mode BatchNorm (batch statistics) and the backward through the encoder are not built."""
+The modules only HOLD parameters; the forward runs in libdiffassemble_hip.so (kNN, vector-neuron layers and pooling as HIP
+kernels; no torch fallback):
+* eval(): ``diffassemble_amd.pcd_encoder.PcdEncoderEngine`` (BatchNorm on the running statistics);
+* train(): ``diffassemble_amd.pcd_encoder.PcdTrainEngine`` -- BatchNorm on the batch statistics, every BatchNorm buffer
+  (VnInv's included) updated in place with the module's momentum / eps, and, under grad, one autograd node
+  (``PcdTrainFunction``) whose backward gives the gradients of every live parameter and of the points.  Like the
+  reference, VnInv's parameters and (unless ``inv``) linear0's get no gradient, and one fragment raises ValueError."""
+import torch
 import torch.nn as nn
 
-from ....pcd_encoder import PcdEncoderEngine
+from ....pcd_encoder import PcdEncoderEngine, PcdTrainEngine
 
 
 class VNBatchNorm(nn.Module):
@@ -55,6 +60,7 @@ class VN_DGCNN(nn.Module):
         self.conv6 = VNLinearLeakyReLU(c * 3, feat_dim, dim=4, share_nonlinearity=True)
         self.linear0 = nn.Linear(3, 2 * feat_dim)
         self._engine, self._engine_key = None, None
+        self._train_engine = None
 
     def engine(self):
         """Packed weights, rebuilt when a parameter / buffer was replaced or modified in place."""
@@ -65,10 +71,20 @@ class VN_DGCNN(nn.Module):
             self._engine_key = key
         return self._engine
 
+    def train_engine(self, chunk=None):
+        """The train-mode engine (packs the live parameters on every call).  ``chunk``: fragments per pass of the
+        backward's per-edge buffers (None: sized by the engine)."""
+        if self._train_engine is None:
+            self._train_engine = PcdTrainEngine(self)
+        if chunk is not None:
+            self._train_engine.chunk = chunk
+        return self._train_engine
+
     def forward(self, x):
         """vn_dgcnn.py:34-74.  x [P, N, 3] (N >= 20) -> [P, 6 feat_dim], or [P, 2 feat_dim] when ``inv``."""
         if self.training:
-            raise NotImplementedError(
-                "the HIP point-cloud encoder implements eval-mode BatchNorm only: call .eval() (sampling / validation) "
-                "or pass precomputed pcd_feats when training")
+            if x.shape[0] == 1:       # what VnInv's BatchNorm1d raises in the reference (vn_dgcnn.py:67)
+                raise ValueError("Expected more than 1 value per channel when training, got input size "
+                                 f"{torch.Size([1, self.VnInv.vn1.map_to_feat.weight.shape[0]])}")
+            return self.train_engine().forward(x, self.inv)
         return self.engine().forward(x)

@@ -586,6 +586,56 @@ int da_pcd_encoder_forward(const da_pcd_encoder_weights *w, int n_parts, int n_p
  * n_points, k] (cloud-local).  x rows: dim == 3 with stride ldx >= 3, or 4 <= dim <= 64 as zero-padded 64-float rows. */
 int da_knn(int n_clouds, int n_points, int dim, const float *x, int ldx, int k, int32_t *idx, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Training path of the 3D piece encoder (SURVEY.md 8f rank 4 in train() mode): VN_DGCNN.forward with batch-statistics
+ * BatchNorm (backbones/vnn/vn_dgcnn.py:34-74, vnn/vn_layers.py:50-91 VNLinearLeakyReLU, :133-154 VNBatchNorm: BatchNorm2d
+ * over the P*N*20 edges for conv1..conv5, BatchNorm1d over the P*N points for conv6 and over the P fragments for VnInv's
+ * vn1 / vn2, :176-240, whose result vn_dgcnn.py:67 discards) and torch autograd through it, down to the point clouds.
+ * fp32 throughout; every per-channel sum runs in a fixed order (fp64 across blocks): bitwise reproducible.
+ * Layer index l: 0..4 conv1..conv5, 5 conv6, 6 VnInv.vn1, 7 VnInv.vn2.
+ * ------------------------------------------------------------------------------------- */
+enum { DA_PCD_TRAIN_LAYERS = 8 };
+typedef struct da_pcd_train_weights {
+    int32_t feat_dim;                        /* conv6 output channels                                     */
+    int32_t reserved0;
+    const float *premap[DA_PCD_STAGES];      /* as da_pcd_encoder_weights                                 */
+    float *bn_a[DA_PCD_STAGES];              /* as da_pcd_encoder_weights; the scale / shift slots of     */
+    float *conv_b[DA_PCD_STAGES];            /*   bn_a, conv_b and conv6 are WRITTEN by the train forward */
+    float *conv6;                            /*   (batch statistics of the call)                          */
+    const float *linear0;                    /* [2 feat][3] + [2 feat]; read for inv only                 */
+    const float *gamma[DA_PCD_TRAIN_LAYERS], *beta[DA_PCD_TRAIN_LAYERS];       /* BatchNorm affine           */
+    const float *running_mean[DA_PCD_TRAIN_LAYERS], *running_var[DA_PCD_TRAIN_LAYERS];
+    float momentum[DA_PCD_TRAIN_LAYERS], eps[DA_PCD_TRAIN_LAYERS];
+    const float *inv_wf[2], *inv_wd[2];      /* VnInv.vn{1,2}.map_to_feat / map_to_dir [cout][cin]         */
+} da_pcd_train_weights;
+
+/* Parameter gradients in the modules' own layouts ([cout][cin] maps, per-channel affine); every output is ADDED to. */
+typedef struct da_pcd_train_grads {
+    float *wf[6], *wd[6];                    /* conv1..conv6 map_to_feat / map_to_dir                     */
+    float *gamma[6], *beta[6];               /* conv1..conv6 BatchNorm weight / bias                      */
+    float *linear0_w, *linear0_b;            /* inv only (may be NULL otherwise)                          */
+    float *points;                           /* [n_parts][n_points][3], may be NULL                       */
+} da_pcd_train_grads;
+
+/* Saved state of one train forward (what its backward reads): neighbour lists, pooled maps, batch statistics. */
+size_t da_pcd_train_state_bytes(int n_parts, int n_points, int feat_dim);
+/* Scratch of the forward and of the backward; the backward's per-edge buffers cover `chunk` fragments at a time. */
+size_t da_pcd_train_workspace_bytes(int n_parts, int n_points, int chunk, int feat_dim);
+
+/* vn_dgcnn.py:34-74 in train(): points [n_parts, n_points, 3] -> out as da_pcd_encoder_forward.  n_parts >= 2
+ * (BatchNorm1d of VnInv over the fragments needs two), n_points >= 20.  run_out [8][2][256]: the updated running mean
+ * (row 2 l) and running variance (row 2 l + 1, unbiased batch variance) of layer l, momentum / eps from `w`. */
+int da_pcd_train_forward(const da_pcd_train_weights *w, int n_parts, int n_points, const float *points, int inv, float *out,
+                         int ld_out, float *run_out, void *state, size_t state_bytes, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
+/* Backward of that call (torch autograd of vn_dgcnn.py:34-74 with batch-statistics BatchNorm): grad_out [n_parts, ld_g]
+ * -> the parameter and point gradients of `g` (added to).  `w` and `state` as left by the forward (the backward writes
+ * its BatchNorm sums into the state's records). */
+int da_pcd_train_backward(const da_pcd_train_weights *w, int n_parts, int n_points, const float *points, int inv,
+                          const float *grad_out, int ld_g, void *state, const da_pcd_train_grads *g, void *workspace,
+                          size_t workspace_bytes, int chunk, void *stream);
+
 /* Nearest-neighbour squared distances both ways (chamfer_distance.py:148-149 = pytorch3d knn_points K = 1, used by
  * utils_3d.py:1089-1129 calc_part_acc): a [n_clouds, n, 3], b [n_clouds, m, 3] -> d_ab [n_clouds, n],
  * d_ba [n_clouds, m]; either output may be NULL. */
