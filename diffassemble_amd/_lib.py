@@ -17,7 +17,7 @@ DA_MAX_LAYERS = 8
 ABI_VERSION = 19
 PREC_F32, PREC_BF16 = 0, 1
 VARIANT_2D, VARIANT_3D = 0, 1
-ARCH_TRANSFORMER, ARCH_EXOPHORMER = 0, 1
+ARCH_TRANSFORMER, ARCH_EXOPHORMER, ARCH_GCN = 0, 1, 2
 MEAN_EPSILON, MEAN_START_X = 0, 1
 ACT_NONE, ACT_GELU, ACT_LEAKY02 = 0, 1, 2
 CONV_Q_PRESCALED, CONV_FOLDED_V32 = 1, 2
@@ -55,7 +55,7 @@ class DaGraph(C.Structure):
         ("max_graph_nodes", C.c_int32), ("n_pad", C.c_int32),
         ("pad_ptr", _fp), ("row_map", _fp),
         ("out_ptr", _fp), ("out_dst", _fp),
-        ("hybrid", C.c_int32), ("reserved0", C.c_int32),
+        ("hybrid", C.c_int32), ("band_degree", C.c_int32),
         ("mask", _fp), ("mask_ptr", _fp), ("irr_row_ptr", _fp), ("irr_col_src", _fp),
         ("slot_node", _fp), ("blk_class", _fp), ("blk_class_ptr", _fp), ("blk_class_stride", C.c_int32), ("reserved1", C.c_int32),
         ("rm_meta", _fp), ("agg_row_ptr", _fp), ("agg_col_src", _fp), ("agg_mult", _fp),
@@ -137,6 +137,8 @@ PROTOTYPES = {
     "da_denoiser_create": (C.c_int, [C.POINTER(DaWeights), C.c_int, _fp, C.POINTER(_fp)]),
     "da_denoiser_destroy": (None, [_fp]),
     "da_denoiser_flags": (C.c_int, [_fp]),
+    "da_gcn_dinv": (C.c_int, [C.POINTER(DaGraph), _fp, _fp]),
+    "da_gcn_aggregate": (C.c_int, [C.c_int, C.POINTER(DaGraph), C.c_int, _fp, _fp, _fp, C.c_int, _fp, _fp]),
     "da_denoiser_workspace_bytes": (C.c_size_t, [_fp, C.POINTER(DaGraph)]),
     "da_denoiser_set_features": (C.c_int, [_fp, C.POINTER(DaGraph), _fp, _fp, C.c_size_t, _fp]),
     "da_denoiser_forward": (C.c_int, [_fp, C.POINTER(DaGraph), _fp, _fp, C.c_int64, _fp, _fp, C.c_int, _fp, _fp,

@@ -153,6 +153,7 @@ struct Workspace {
     unsigned *virt_cnt;               // hybrid graphs with virtual rows: arrival counters of the rows' workgroups (inside the zero-filled region) ...
     float *virt_part;                 // ... and their partial softmax states (AttnDenseParams::v_cnt / v_part)
     float *model_out, *xbuf0, *xbuf1;
+    float *gcn_dinv;                  // GCN arch, CSR plans: deg^-1/2 per node (da_gcn.hip), once per Batch
     size_t total;
 };
 
@@ -177,7 +178,8 @@ static Workspace carve(const da_denoiser *d, const da_graph *g, void *base) {
     w.head_pre = take(nrp * 32 * s);
     w.pz = take(nrp * 32 * (size_t)d->heads * sizeof(float));
     w.combined = take(np * d->D * s);
-    w.qkvs = take(np * 4 * (size_t)hcmax * s);
+    const bool gcn = d->arch == DA_ARCH_GCN;           // (the GCN reads none of the attention buffers: xa / xb / z / combined only)
+    w.qkvs = take(gcn ? 0 : np * 4 * (size_t)hcmax * s);
     w.xa = take(np * 256 * s);
     w.xb = take(np * 256 * s);
     w.z = take(np * d->D * s);
@@ -186,7 +188,7 @@ static Workspace carve(const da_denoiser *d, const da_graph *g, void *base) {
     w.virt_cnt = nullptr; w.virt_part = nullptr;
     w.dense_off = off;
     w.dense_bytes = 0;
-    if ((g->dense || g->hybrid) && g->n_pad > 0) {
+    if ((g->dense || g->hybrid) && g->n_pad > 0 && !gcn) {
         const size_t hb = ((size_t)g->n_pad + 64) * hcmax * s;
         w.dq = take(hb);
         w.dk = take(hb);
@@ -201,6 +203,7 @@ static Workspace carve(const da_denoiser *d, const da_graph *g, void *base) {
     w.model_out_unc = (float *)take(nr * cpose * sizeof(float));
     w.xbuf0 = (float *)take(nr * 8 * sizeof(float));
     w.xbuf1 = (float *)take(nr * 8 * sizeof(float));
+    w.gcn_dinv = d->arch == DA_ARCH_GCN ? (float *)take(n * sizeof(float)) : nullptr;
     w.total = off;
     return w;
 }
@@ -323,6 +326,21 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
     // (a-4..a-6) graph transformer: fused Q|K|V|skip projection + attention per layer
     const void *xin = fused ? w.h : w.combined;
     int ldx = fused ? d->hidden : D;
+    if (d->arch == DA_ARCH_GCN) {
+        // backbones/gcn.py:16-22, gelu(conv1(gelu(conv0(x)))), reassociated so that both aggregations run 256 wide:
+        // conv 0 projects first (A_hat (X W0^T)), conv 1 aggregates first ((A_hat H) W1^T); the residual `feats + combined_feats`
+        // (efficient_gat.py:144 / efficient_gat_3d.py:199) is added in the epilogue of conv 1's GEMM, after its GELU
+        const ConvW &c0 = d->conv[0], &c1 = d->conv[1];
+        const int hid = c0.hc;
+        if ((rc = timed(d, DA_PROF_LINEAR_QKVS, st, [&] {
+                 return linear(prec, nr, D, hid, w.combined, D, c0.w, nullptr, DA_ACT_NONE, nullptr, w.xa, hid, st); }))) return rc;
+        if ((rc = timed(d, DA_PROF_ATTN_HIDDEN, st, [&] {
+                 return launch_gcn_aggregate(prec, g, hid, w.gcn_dinv, w.xa, c0.b, DA_ACT_GELU, w.xb, st); }))) return rc;
+        if ((rc = timed(d, DA_PROF_ATTN_LAST, st, [&] {
+                 return launch_gcn_aggregate(prec, g, hid, w.gcn_dinv, w.xb, nullptr, DA_ACT_NONE, w.xa, st); }))) return rc;
+        if ((rc = timed(d, DA_PROF_LINEAR_QKVS, st, [&] {
+                 return linear(prec, nr, hid, D, w.xa, hid, c1.w, c1.b, DA_ACT_GELU, w.combined, w.z, D, st); }))) return rc;
+    } else
     for (int l = 0; l < d->n_layers; ++l) {
         ConvW c = d->conv[l];
         if (fused && l == 0) { c.w = d->conv0c_w; c.b = d->conv0c_b; c.din = d->hidden; }
@@ -540,6 +558,8 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
     DA_REQUIRE(w && out, "da_denoiser_create: null argument");
     DA_REQUIRE(precision == DA_PREC_F32 || precision == DA_PREC_BF16, "bad precision %d", precision);
     DA_REQUIRE(w->n_layers >= 2 && w->n_layers <= DA_MAX_LAYERS, "n_layers out of range");
+    DA_REQUIRE(w->arch == DA_ARCH_TRANSFORMER || w->arch == DA_ARCH_EXOPHORMER || w->arch == DA_ARCH_GCN, "bad arch %d", w->arch);
+    DA_REQUIRE(w->arch != DA_ARCH_GCN || w->n_layers == 2, "gcn arch: n_layers must be 2 (backbones/gcn.py:9-14)");
     DA_REQUIRE(w->heads == 8, "heads must be 8");
     // k_embed_pos_time keeps the pose-MLP weight rows in a fixed register array (da_basic.hip); fail here, not on the first
     // forward or inside a hipGraph capture (the reference uses c_in = 2 / 4 in 2D and 7 in 3D)
@@ -594,7 +614,20 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
     d->mlp_w0 = pack(w->mlp_w0, (size_t)d->hidden * D); d->mlp_b0 = copy_f32(w->mlp_b0, d->hidden);
     d->mlp_w1 = pack(w->mlp_w1, (size_t)D * d->hidden); d->mlp_b1 = copy_f32(w->mlp_b1, D);
     if (rc) return fail(rc);
-    for (int l = 0; l < d->n_layers; ++l) {
+    if (d->arch == DA_ARCH_GCN) {
+        // GCNConv(D, 256), GCNConv(256, D) (gcn.py:9-14): lin.weight [out, in] packed in the act dtype (no bias in lin), bias fp32
+        for (int l = 0; l < 2; ++l) {
+            ConvW &c = d->conv[l];
+            c.din = l == 0 ? D : 256;
+            c.hc = l == 0 ? 256 : D;
+            if (!w->conv_wq[l] || !w->conv_bq[l]) { set_error("gcn conv %d: missing weight pointer", l); return fail(1); }
+            c.w = pack(w->conv_wq[l], (size_t)c.hc * c.din);
+            c.b = copy_f32(w->conv_bq[l], c.hc);
+            c.wd = c.w; c.bd = c.b;
+            if (rc) return fail(rc);
+        }
+    }
+    for (int l = 0; l < (d->arch == DA_ARCH_GCN ? 0 : d->n_layers); ++l) {
         ConvW &c = d->conv[l];
         c.din = l == 0 ? D : 32 * H;
         c.C = l == d->n_layers - 1 ? D / H : 32;
@@ -652,7 +685,7 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
     if (rc) return fail(rc);
     {
         const bool off = (cfg().disable_folds & DA_FOLD_MLP2) != 0;
-        if (!off && !mfma_disabled() && d->variant == DA_VARIANT_2D && d->hidden % 32 == 0) {
+        if (!off && !mfma_disabled() && d->variant == DA_VARIANT_2D && d->hidden % 32 == 0 && d->arch != DA_ARCH_GCN) {
             // compose in fp32 from the caller's fp32 weights, then pack
             const int hid = d->hidden, hc0 = d->conv[0].hc;
             float *w2t = (float *)alloc((size_t)hid * D * 4);                  // W2^T [hidden, D]
@@ -753,6 +786,7 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
     }
     d->dense_only = d->heads == 8 && !dense_disabled() && !mfma_disabled();
     for (int l = 0; l < d->n_layers; ++l) d->dense_only = d->dense_only && (d->conv[l].C == 32 || d->conv[l].C == 144);
+    if (d->arch == DA_ARCH_GCN) d->dense_only = true;     // complete / banded plans aggregate in closed form (da_gcn.hip): no CSR
     *out = d;
     return 0;
 }
@@ -810,6 +844,7 @@ int da_denoiser_set_features(da_denoiser *d, const da_graph *g, const float *fea
     }
     if (w.dense_bytes)      // padded rows / columns of the head-major buffers must be finite
         DA_CHECK_HIP(hipMemsetAsync((char *)workspace + w.dense_off, 0, w.dense_bytes, st));
+    if (d->arch == DA_ARCH_GCN && (rc = launch_gcn_dinv(g, w.gcn_dinv, st))) return rc;
     if (d->V > 0) {
         char *dst = w.combined + (size_t)g->n_real * d->D * esize(d->prec);
         if ((rc = launch_set_virtual_rows(d->prec, g->n_nodes - g->n_real, d->V, d->D, d->virt_emb, dst, st))) return rc;
@@ -823,6 +858,7 @@ int da_denoiser_forward(da_denoiser *d, const da_graph *g, const float *x, const
     DA_REQUIRE(d && g && x && out && workspace, "da_denoiser_forward: null argument");
     int rc = check_graph(d, g);
     if (rc) return rc;
+    DA_REQUIRE(!alpha || d->arch != DA_ARCH_GCN, "alpha requested from a GCN denoiser: GCN.forward returns no attention weights (gcn.py:22)");
     DA_REQUIRE(!alpha || g->edge_id, "alpha requested but graph has no edge_id");
     Workspace w = carve(d, g, workspace);
     DA_REQUIRE(workspace_bytes >= w.total, "workspace too small: %zu < %zu", workspace_bytes, w.total);

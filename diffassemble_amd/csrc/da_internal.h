@@ -228,6 +228,14 @@ int pcd_edge_launch(const float *T, const int32_t *idx, const float *bn_a, const
 int pcd_conv6_final_launch(const float *X1, const float *X2, const float *X3, const float *w6, int feat, int N, int clouds,
                            float *partial, const float *lin0, int inv, float *out, int ldo, hipStream_t st);
 
+// da_gcn.hip: the GCN backbone's aggregation (0 = dense, 1 = band, 2 = csr, -1 = no path for this plan)
+int gcn_plan_kind(const da_graph *g);
+int launch_gcn_dinv(const da_graph *g, float *dinv, hipStream_t st);
+int launch_gcn_aggregate(int prec, const da_graph *g, int W, const float *dinv, const void *X, const float *bias, int act, void *out,
+                         hipStream_t st);
+int launch_gcn_aggregate_t(int prec, const da_graph *g, int W, const float *dinv, const void *X, void *out, hipStream_t st);   // A_hat^T X
+int launch_gcn_gelu_res(size_t n, const float *pre, const float *res, float *out, hipStream_t st);                           // gelu(pre) + res
+
 // generic linear dispatch (MFMA when the shape allows, else simple)
 int linear(int prec, int M, int K, int Nout, const void *A, int lda, const void *W, const float *bias, int act,
            const void *res, void *out, int ldo, hipStream_t st);

@@ -886,6 +886,7 @@ struct Dims {
     int nr, n, F, D, hid, H, L, V, c_in, c_out, G;
     int din[DA_MAX_LAYERS], C[DA_MAX_LAYERS], hc[DA_MAX_LAYERS];
     bool gelu_between;
+    bool gcn;                  // DA_ARCH_GCN (backbones/gcn.py): two GCNConv, aggregation by da_gcn.hip, no attention
     bool dense;                // complete graphs: grouped-GEMM attention (da_train_dense.hip)
     bool hybrid;               // hybrid graphs: masked grouped GEMMs + CSR remainder (da_train_dense.hip)
     bool bfc;                  // DA_TRAIN_MMA_BF16: GEMM operands rounded to bf16 inside the matrix-core kernels (storage stays fp32)
@@ -900,16 +901,26 @@ static int dims_of(const da_weights *w, const da_graph *g, Dims &d, int mma = DA
     d.bfc = mma == DA_TRAIN_MMA_BF16;
     DA_REQUIRE(w && g, "training: null argument");
     DA_REQUIRE(w->variant == DA_VARIANT_2D, "training: only the 2D denoiser is implemented");
+    d.gcn = w->arch == DA_ARCH_GCN;
+    DA_REQUIRE(!d.gcn || w->n_layers == 2, "training: gcn arch needs n_layers = 2 (backbones/gcn.py:9-14)");
     DA_REQUIRE(w->heads == 8 && w->n_layers >= 2 && w->n_layers <= DA_MAX_LAYERS, "training: bad heads / n_layers");
     d.nr = g->n_real; d.n = g->n_nodes; d.F = w->feat_dim; d.D = w->feat_dim + 64; d.hid = w->hidden; d.H = w->heads;
     d.L = w->n_layers; d.V = w->arch == DA_ARCH_EXOPHORMER ? w->virt_nodes : 0; d.c_in = w->c_in; d.c_out = w->c_out;
-    d.gelu_between = w->arch == DA_ARCH_TRANSFORMER;
+    d.gelu_between = w->arch == DA_ARCH_TRANSFORMER || d.gcn;
     d.G = g->n_graphs;
     DA_REQUIRE(d.D % d.H == 0 && (d.D / d.H) % 8 == 0, "training: D / heads must be a multiple of 8");
     for (int l = 0; l < d.L; ++l) {
         d.din[l] = l == 0 ? d.D : 32 * d.H;
         d.C[l] = l == d.L - 1 ? d.D / d.H : 32;
         d.hc[l] = d.C[l] * d.H;
+        if (d.gcn) { d.hc[l] = l == 0 ? 256 : d.D; d.din[l] = l == 0 ? d.D : 256; d.C[l] = 0; }     // GCNConv(D, 256), GCNConv(256, D)
+    }
+    if (d.gcn) {          // aggregation in closed form (complete graphs, banded Exphander plans) or over the CSR (da_gcn.hip)
+        d.dense = d.hybrid = false;
+        d.q16 = false;
+        d.pair_floats = 0;
+        DA_REQUIRE(gcn_plan_kind(g) >= 0, "training (gcn): plan the Batch without the hybrid split (build_plan(..., hybrid='off'))");
+        return 0;
     }
     DA_REQUIRE(g->n_real > 0 && g->n_nodes >= g->n_real, "training: bad graph");
     DA_REQUIRE(d.V == 0 || g->n_nodes == g->n_real + d.V * g->n_graphs, "training: exophormer expects n_nodes = n_real + V*G");
@@ -952,7 +963,7 @@ static TrainWs carve_train(const Dims &d, void *base) {
     for (int l = 0; l < d.L; ++l) {
         w.qkvs[l] = take(n * 4 * d.hc[l]);
         w.o[l] = take(n * d.hc[l]);
-        w.hact[l] = (l < d.L - 1 && d.gelu_between) ? take(n * d.hc[l]) : nullptr;
+        w.hact[l] = ((l < d.L - 1 && d.gelu_between) || d.gcn) ? take(n * d.hc[l]) : nullptr;      // (gcn, last layer: z = gelu(pre) + h0)
         w.stats[l] = take(n * d.H * 2);
         hcmax = d.hc[l] > hcmax ? d.hc[l] : hcmax;
         const size_t ws = (size_t)4 * d.hc[l] * d.din[l];
@@ -1002,7 +1013,9 @@ static TrainWs carve_train(const Dims &d, void *base) {
 }
 
 static int check_fused(const da_weights *w, const Dims &d, const char *what) {
-    for (int l = 0; l < d.L; ++l) {
+    for (int l = 0; l < d.L && d.gcn; ++l)
+        DA_REQUIRE(w->conv_wq[l] && w->conv_bq[l], "%s: gcn conv %d pointers (lin.weight, bias) missing", what, l);
+    for (int l = 0; l < d.L && !d.gcn; ++l) {
         const size_t blk = (size_t)d.hc[l] * d.din[l];
         DA_REQUIRE(w->conv_wq[l] && w->conv_bq[l], "%s: conv %d pointers missing", what, l);
         DA_REQUIRE(w->conv_wk[l] == w->conv_wq[l] + blk && w->conv_wv[l] == w->conv_wq[l] + 2 * blk &&
@@ -1035,7 +1048,8 @@ static int weight_prep(const da_weights *w, const Dims &d, TrainWs &ws, hipStrea
     add(w->mlp_w1, ws.wt_mlp1, d.D, d.hid, 0);
     add(w->mlp_w0, ws.wt_mlp0, d.hid, d.D, 0);
     add(w->pos_w1, ws.wt_pos1, 32, 16, 0);
-    for (int l = 0; l < d.L; ++l) {
+    for (int l = 0; l < d.L && d.gcn; ++l) add(w->conv_wq[l], ws.wt_conv[l], d.hc[l], d.din[l], 0);       // GCNConv lin.weight^T
+    for (int l = 0; l < d.L && !d.gcn; ++l) {
         add(w->conv_wq[l], ws.wt_conv[l], 4 * d.hc[l], d.din[l], d.q16 ? 1 : 0);
         if (d.q16) add(w->conv_wq[l], ws.wh_conv[l], 4 * d.hc[l], d.din[l], 2);
     }
@@ -1223,6 +1237,21 @@ int da_train_forward_ex(const da_weights *w, const da_graph *g, const float *x, 
         if ((rc = launch_set_virtual_rows(P, n - nr, d.V, D, w->virt_emb, ws.h0 + (size_t)nr * D, st))) return rc;
     }
     if (sd) { DA_CHECK_HIP(hipStreamWaitEvent(st, ev_images, 0)); side_guard.armed = false; }      // the weight images are there (nothing else runs on the side stream in a forward)
+    if (d.gcn) {
+        // gcn.py:16-22 with the inference path's reassociation: P0 = h0 W0^T, pre0 = A_hat P0 + b0, a0 = gelu(pre0),
+        // Y = A_hat a0, pre1 = Y W1^T + b1, z = gelu(pre1) + h0.  Saved for the backward: qkvs[0] = P0 (unused), o[0] = pre0,
+        // hact[0] = a0, qkvs[1] = Y, o[1] = pre1, hact[1] = z, Dd = dinv (CSR plans)
+        float *dinv = ws.Dd;
+        if ((rc = launch_gcn_dinv(g, dinv, st))) return rc;
+        if ((rc = linear(PL, n, D, d.hc[0], ws.h0, D, w->conv_wq[0], nullptr, DA_ACT_NONE, nullptr, ws.qkvs[0], d.hc[0], st))) return rc;
+        if ((rc = launch_gcn_aggregate(P, g, d.hc[0], dinv, ws.qkvs[0], w->conv_bq[0], DA_ACT_NONE, ws.o[0], st))) return rc;
+        if ((rc = gelu_fwd((size_t)n * d.hc[0], ws.o[0], ws.hact[0], st))) return rc;
+        if ((rc = launch_gcn_aggregate(P, g, d.hc[0], dinv, ws.hact[0], nullptr, DA_ACT_NONE, ws.qkvs[1], st))) return rc;
+        if ((rc = linear(PL, n, d.hc[0], D, ws.qkvs[1], d.hc[0], w->conv_wq[1], w->conv_bq[1], DA_ACT_NONE, nullptr, ws.o[1], D, st))) return rc;
+        if ((rc = launch_gcn_gelu_res((size_t)n * D, ws.o[1], ws.h0, ws.hact[1], st))) return rc;
+        if ((rc = linear_fw(d, ws, nr, D, 32, ws.hact[1], D, w->head_w0, w->head_b0, ws.f1pre, 32, st, ws.f1))) return rc;
+        return launch_head2d(P, nr, d.c_out, ws.f1, w->head_w1, w->head_b1, out, st);
+    }
     const float *xin = ws.h0;
     int ldx = D;
     bool x16_ready = false;           // x16[l] already holds the bf16 image of xin (written by the GELU launch of the layer before)
@@ -1304,7 +1333,7 @@ int da_train_backward_stage(const da_weights *w, const da_weights *grads, const 
     DA_REQUIRE(mma_precision == DA_TRAIN_MMA_FP32 || mma_precision == DA_TRAIN_MMA_BF16, "da_train_backward: unknown mma_precision %d", mma_precision);
     if ((rc = dims_of(w, g, d, mma_precision))) return rc;
     DA_REQUIRE(grads && x && t && d_out && workspace, "da_train_backward: null argument");
-    DA_REQUIRE(d.dense || (g->out_ptr && (g->out_dst || d.hybrid)), "da_train_backward: the graph needs the by-source CSR (out_ptr / "
+    DA_REQUIRE(d.dense || (d.gcn && gcn_plan_kind(g) != 2) || (g->out_ptr && (g->out_dst || d.hybrid)), "da_train_backward: the graph needs the by-source CSR (out_ptr / "
                "out_dst; of the remainder edges for hybrid graphs, where out_dst may be empty)");
     if ((rc = check_fused(w, d, "da_train_backward(weights)"))) return rc;
     if ((rc = check_fused(grads, d, "da_train_backward(grads)"))) return rc;
@@ -1324,7 +1353,7 @@ int da_train_backward_stage(const da_weights *w, const da_weights *grads, const 
     // ---- head: final_mlp.2, GELU, final_mlp.0 (efficient_gat.py:145)
     if ((rc = linear_bwd(nr, d.c_out, 32, d_out, d.c_out, ws.f1, 32, ws.wt_head1, G(grads->head_w1), G(grads->head_b1),
                          ws.df1, 32, nullptr, ws, st, d.bfc, false, ws.f1pre, nullptr, sd))) return rc;
-    const float *z = ws.o[L - 1];
+    const float *z = d.gcn ? ws.hact[L - 1] : ws.o[L - 1];
     if (n > nr) DA_CHECK_HIP(hipMemsetAsync(ws.dz + (size_t)nr * D, 0, (size_t)(n - nr) * D * 4, st));
     if ((rc = linear_bwd(nr, 32, D, ws.df1, 32, z, D, ws.wt_head0, G(grads->head_w0), G(grads->head_b0), ws.dz, D, nullptr,
                          ws, st, d.bfc, false, nullptr, nullptr, sd))) return rc;
@@ -1333,10 +1362,28 @@ int da_train_backward_stage(const da_weights *w, const da_weights *grads, const 
     if (dh0_copy) DA_CHECK_HIP(hipMemcpyAsync(ws.dh0, ws.dz, (size_t)n * D * 4, hipMemcpyDeviceToDevice, st));
     }
 
+    if (d.gcn) {
+        // ---- GCN (gcn.py:16-22), EARLY: conv 1 -- z = gelu(pre1) + h0, pre1 = Y W1^T + b1
+        const int hid = d.hc[0];
+        if (do_early) {
+            if ((rc = gelu_bwd((size_t)n * D, ws.o[1], ws.dz, ws.dxa, st))) return rc;                      // d pre1
+            if ((rc = linear_bwd(n, D, hid, ws.dxa, D, ws.qkvs[1], hid, ws.wt_conv[1], G(grads->conv_wq[1]), G(grads->conv_bq[1]),
+                                 ws.dxb, hid, nullptr, ws, st, d.bfc, false, nullptr, nullptr, sd))) return rc;  // dW1, db1, dY
+        }
+        // LATE: conv 0 -- Y = A_hat a0, a0 = gelu(pre0), pre0 = A_hat P0 + b0, P0 = h0 W0^T; dh0 = dz (residual) + dP0 W0
+        if (do_late) {
+            if ((rc = launch_gcn_aggregate_t(DA_PREC_F32, g, hid, ws.Dd, ws.dxb, ws.dY4, st))) return rc;     // d a0 = A_hat^T dY
+            if ((rc = gelu_bwd((size_t)n * hid, ws.o[0], ws.dY4, ws.dY4, st))) return rc;                     // d pre0
+            if ((rc = colsum_add(n, hid, ws.dY4, hid, G(grads->conv_bq[0]), ws.partial, st))) return rc;     // db0 (bias after the aggregation)
+            if ((rc = launch_gcn_aggregate_t(DA_PREC_F32, g, hid, ws.Dd, ws.dY4, ws.dY4b, st))) return rc;    // d P0 = A_hat^T d pre0
+            if ((rc = linear_bwd(n, hid, D, ws.dY4b, hid, ws.h0, D, ws.wt_conv[0], G(grads->conv_wq[0]), nullptr, ws.dh0, D, ws.dz,
+                                 ws, st, d.bfc, false, nullptr, nullptr, sd))) return rc;                      // dW0, dh0
+        }
+    }
     // ---- graph transformer layers, last to first (EARLY: L-1 .. 1; LATE: 0, whose incoming gradient is layer 1's dX buffer)
     const float *d_o = do_early ? ws.dz : (L > 1 ? ws.dxa : ws.dz);
     const int l_first = do_early ? L - 1 : 0;
-    for (int l = l_first; l >= (do_late ? 0 : 1); --l) {
+    for (int l = l_first; !d.gcn && l >= (do_late ? 0 : 1); --l) {
         const int hc = d.hc[l], din = d.din[l];
         // this layer's projection gradient: the two buffers alternate, and the one about to be overwritten was last read by layer
         // l + 2's dW product on the side stream

@@ -63,7 +63,7 @@ class DenoiserEngine:
         self.c_in = sd["pos_mlp.0.weight"].shape[1]
         self.steps = sd["time_emb.weight"].shape[0]
         w.variant = _lib.VARIANT_3D if variant == "3d" else _lib.VARIANT_2D
-        w.arch = _lib.ARCH_EXOPHORMER if arch == "exophormer" else _lib.ARCH_TRANSFORMER
+        w.arch = {"exophormer": _lib.ARCH_EXOPHORMER, "gcn": _lib.ARCH_GCN}.get(arch, _lib.ARCH_TRANSFORMER)
         w.steps, w.c_in, w.feat_dim = self.steps, self.c_in, self.F
         w.hidden = sd["mlp.0.weight"].shape[0]
         w.heads, w.n_layers, w.virt_nodes = 8, self.n_layers, self.virt_nodes
@@ -74,6 +74,9 @@ class DenoiserEngine:
         w.mlp_w1, w.mlp_b1 = P("mlp.2.weight"), P("mlp.2.bias")
         for l in layers:
             p = f"gnn_backbone.module_list.{l}."
+            if arch == "gcn":              # GCNConv: lin.weight [out, in] (no bias in lin), bias added after the aggregation
+                w.conv_wq[l], w.conv_bq[l] = P(p + "lin.weight"), P(p + "bias")
+                continue
             w.conv_wq[l], w.conv_bq[l] = P(p + "lin_query.weight"), P(p + "lin_query.bias")
             w.conv_wk[l], w.conv_bk[l] = P(p + "lin_key.weight"), P(p + "lin_key.bias")
             w.conv_wv[l], w.conv_bv[l] = P(p + "lin_value.weight"), P(p + "lin_value.bias")
@@ -117,12 +120,23 @@ class DenoiserEngine:
 
     # ------------------------------------------------------------------ graph + workspace
     def plan(self, edge_index, batch):
-        return build_plan(edge_index.to(self.device), batch.to(self.device), self.virt_nodes)
+        # the GCN aggregates complete graphs in closed form and everything else over the CSR: no adjacency-mask split
+        return build_plan(edge_index.to(self.device), batch.to(self.device), self.virt_nodes,
+                          hybrid="off" if self.arch == "gcn" else None)
 
     def plan_expander(self, perms, degree):
-        """Plan of a Batch of Exphander graphs straight from their permutations (no edge list, no sort)."""
+        """Plan of a Batch of Exphander graphs straight from their permutations (no edge list, no sort).
+        GCN: the banded layout (closed-form aggregation, da_graph.band_degree); shapes without it -- duplicated edges, graphs
+        too large for the banded slots -- are planned over the CSR."""
         from .graph_plan import expander_plan
-        return expander_plan(perms, degree, self.device, self.virt_nodes)
+        if self.arch != "gcn":
+            return expander_plan(perms, degree, self.device, self.virt_nodes)
+        plan = expander_plan(perms, degree, self.device, 0, banded=True)
+        if plan.hybrid and not plan.band_degree:
+            G, n = plan.n_graphs, plan.max_graph_nodes
+            batch = torch.arange(G, device=self.device).repeat_interleave(n)
+            plan = build_plan(plan.edge_index, batch, 0, hybrid="off")
+        return plan
 
     def _workspace(self, plan: GraphPlan, need_csr=None):
         if need_csr is None:       # complete / hybrid graphs on an all-MFMA denoiser never walk the edge list
@@ -148,6 +162,8 @@ class DenoiserEngine:
     def forward(self, plan, x, t, feats=None, return_alpha=False, return_pre_head=False, alpha_all_layers=False):
         """Eff_GAT(.._3d).forward_with_feats.  ``feats=None`` reuses the features already staged
         for this plan (sampling loop).  t: int64 [N] tensor or python int."""
+        if return_alpha and self.arch == "gcn":
+            raise _lib.DaError("the GCN arch has no attention weights (GCN.forward returns (x, None), gcn.py:22)")
         if return_alpha:
             plan.ensure_csr()              # alpha[E, H] is produced by the edge-list kernels
         if feats is not None:
@@ -476,6 +492,26 @@ def attn_csr(plan: GraphPlan, qkvs, heads, C_head, residual=None, act=_lib.ACT_N
     _lib.check(_lib.lib().da_attn_csr(prec, C.byref(g), heads, C_head, _lib.ptr(qkvs), _lib.ptr(r), int(act),
                                       _lib.ptr(out), _lib.ptr(alpha), _lib.stream_ptr(qkvs.device)))
     return (out, alpha) if return_alpha else out
+
+
+def gcn_aggregate(plan: GraphPlan, x, bias=None, act=_lib.ACT_NONE, precision="fp32"):
+    """act(D^-1/2 (A' + I) D^-1/2 x + bias) of PyG's GCNConv (the aggregation only) through da_gcn_aggregate: x [n_nodes, W],
+    W % 4 == 0.  Complete graphs and banded Exphander plans in closed form, other plans over the CSR (dinv from da_gcn_dinv)."""
+    prec = _PREC[precision]
+    dt = torch.bfloat16 if prec == _lib.PREC_BF16 else torch.float32
+    x = x.to(dt).contiguous()
+    out = torch.empty_like(x)
+    b = None if bias is None else bias.float().contiguous()
+    need_csr = not (plan.dense or (plan.hybrid and plan.band_degree))
+    g = plan.c_struct(need_csr)
+    dinv = torch.empty(plan.n_nodes, dtype=torch.float32, device=x.device) if need_csr else None
+    lib = _lib.lib()
+    with torch.cuda.device(x.device):
+        if dinv is not None:
+            _lib.check(lib.da_gcn_dinv(C.byref(g), _lib.ptr(dinv), _lib.stream_ptr(x.device)))
+        _lib.check(lib.da_gcn_aggregate(prec, C.byref(g), x.shape[1], _lib.ptr(dinv), _lib.ptr(x), _lib.ptr(b), int(act), _lib.ptr(out),
+                                        _lib.stream_ptr(x.device)))
+    return out
 
 
 def conv_dense(plan: GraphPlan, x, weight, bias, heads, C_head, residual=None, act=_lib.ACT_NONE, precision="fp32"):

@@ -75,6 +75,7 @@ class GraphPlan:
     blk_class_stride: int = 0
     rm_meta: torch.Tensor = None       # int32 [n_pad, 4]: per slot (remainder begin, end, slot of the first remainder source, node)
     agg: tuple = None                  # (row_ptr int32 [n_nodes + 1], col_src int32, mult float32): virtual rows' remainder edges, duplicates merged
+    band_degree: int = 0               # banded Exphander plans: the degree d (da_graph.band_degree; the GCN aggregates them in closed form)
 
     @property
     def edge_index(self):
@@ -144,6 +145,7 @@ class GraphPlan:
         g.out_ptr = self.out_ptr.data_ptr() if self.out_ptr is not None else None
         g.out_dst = self.out_dst.data_ptr() if self.out_dst is not None else None
         g.hybrid = self.hybrid
+        g.band_degree = self.band_degree
         if self.hybrid:
             g.mask, g.mask_ptr = self.mask.data_ptr(), self.mask_ptr.data_ptr()
             g.irr_row_ptr, g.irr_col_src = self.irr_row_ptr.data_ptr(), self.irr_col_src.data_ptr()
@@ -560,7 +562,8 @@ def _expander_plan_banded(perms, d, V, sh, edge_list, E):
         n_nodes=N + V * G, n_real=N, n_graphs=G, dense=0, n_edges=E, max_graph_nodes=n,
         row_ptr=None, col_src=None, edge_id=None, graph_ptr=sh["graph_ptr32"], _edge_index=None,
         edge_index_fn=edge_list, hybrid=1, mask=band["mask"], mask_ptr=zero_ptr, irr_row_ptr=sh["irr_ptr"], irr_col_src=sh["irr_src"],
-        slot_node=slot_node.reshape(-1).contiguous(), blk_class=band["cls"], blk_class_ptr=zero_ptr, blk_class_stride=band["stride"])
+        slot_node=slot_node.reshape(-1).contiguous(), blk_class=band["cls"], blk_class_ptr=zero_ptr, blk_class_stride=band["stride"],
+        band_degree=d if V == 0 else 0)
 
 
 def _detect_dense(edge_index, batch, counts):

@@ -5,6 +5,7 @@ architectures the drivers merely import are placeholders that fail on constructi
 from .efficient_gat import Eff_GAT
 from .efficient_gat_3d import Eff_GAT_3d
 from .exophormer_gnn import Exophormer_GNN
+from .gcn import GCN, GCNConv
 from .Transformer_GNN import Transformer_GNN
 from .transformer_conv import TransformerConv
 
@@ -24,5 +25,5 @@ Eff_GAT_Discrete = _out_of_scope("Eff_GAT_Discrete")
 Eff_GAT_Discrete_ROT = _out_of_scope("Eff_GAT_Discrete_ROT")
 Eff_GAT_Vist = _out_of_scope("Eff_GAT_Vist")
 
-__all__ = ["Eff_GAT", "Eff_GAT_3d", "Exophormer_GNN", "Transformer_GNN", "TransformerConv",
+__all__ = ["Eff_GAT", "Eff_GAT_3d", "Exophormer_GNN", "GCN", "GCNConv", "Transformer_GNN", "TransformerConv",
            "Dark_TFConv", "Eff_GAT_Discrete", "Eff_GAT_Discrete_ROT", "Eff_GAT_Vist"]

@@ -129,7 +129,9 @@ class DenoiserBase(nn.Module):
         key = getattr(self, "_tplan_key", None)
         if key is None or not key.matches((edge_index, batch), (id(te),)):
             from ...graph_plan import build_plan
-            self._tplan = build_plan(edge_index.to(te.device), batch.to(te.device), te.virt_nodes).with_source_csr()
+            # (the GCN aggregates complete graphs in closed form and everything else over the CSR: no hybrid split)
+            self._tplan = build_plan(edge_index.to(te.device), batch.to(te.device), te.virt_nodes,
+                                     hybrid="off" if te.arch == "gcn" else None).with_source_csr()
             self._tplan_key = _Held((edge_index, batch), (id(te),))
         out = DenoiserTrainFn.apply(te, self._tplan, xy_pos, time, feats, te.anchor)
         return out, None
@@ -140,6 +142,8 @@ class DenoiserBase(nn.Module):
         plan = self._plan_for(eng, edge_index, batch)
         self._stage_features(eng, plan, feats)
         all_layers = self.gnn_backbone.arch == "transformer"
+        if self.gnn_backbone.arch == "gcn":         # GCN.forward returns (x, None) (gcn.py:22): no attention weights
+            return eng.forward(plan, xy_pos, time, None), None
         if return_attentions:
             out, alpha = eng.forward(plan, xy_pos, time, None, return_alpha=True, alpha_all_layers=all_layers)
             attentions = ([(plan.edge_index, alpha[l]) for l in range(alpha.shape[0])] if all_layers

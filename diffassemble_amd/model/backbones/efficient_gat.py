@@ -7,6 +7,7 @@ from torch import Tensor
 
 from ._denoiser_base import DenoiserBase, default_precision
 from .exophormer_gnn import Exophormer_GNN
+from .gcn import GCN
 from .Transformer_GNN import Transformer_GNN
 
 
@@ -42,8 +43,10 @@ class Eff_GAT(DenoiserBase):
         elif architecture == "exophormer":
             self.gnn_backbone = Exophormer_GNN(D, n_layers=n_layers, hidden_dim=32 * 8, heads=8, output_size=D,
                                                virt_nodes=virt_nodes)
+        elif architecture == "gcn":                    # efficient_gat.py:65-70
+            self.gnn_backbone = GCN(D, hidden_dim=32 * 8, output_size=D)
         else:
-            raise NotImplementedError(f"architecture={architecture!r}: the GCN ablation is out of scope")
+            raise NotImplementedError(f"architecture={architecture!r}: not one of transformer / gcn / exophormer")
         self.time_emb = nn.Embedding(steps, 32)
         self.pos_mlp = nn.Sequential(nn.Linear(input_channels, 16), nn.GELU(), nn.Linear(16, 32))
         self.final_mlp = nn.Sequential(nn.Linear(D, 32), nn.GELU(), nn.Linear(32, output_channels))

@@ -42,6 +42,9 @@ def _param_order(module):
         names.append("gnn_backbone.virt_node_embedding.weight")
     for l in range(n_layers):
         p = f"gnn_backbone.module_list.{l}."
+        if module.gnn_backbone.arch == "gcn":         # GCNConv (backbones/gcn.py): lin.weight (no bias in lin), bias
+            names += [p + "lin.weight", p + "bias"]
+            continue
         names += [p + f"lin_{k}.weight" for k in ("query", "key", "value", "skip")]
         names += [p + f"lin_{k}.bias" for k in ("query", "key", "value", "skip")]
     names += ["final_mlp.0.weight", "final_mlp.0.bias", "final_mlp.2.weight", "final_mlp.2.bias"]
@@ -72,7 +75,8 @@ class TrainEngine:
         # data-parallel buckets, in the order backward completes them: EARLY = [early_off, total) = convs 1 .. L-1 and final_mlp
         # (final once da_train_backward_stage(EARLY) has run), LATE = [0, early_off) = embeddings, mlp, virtual nodes, conv 0
         # (a one-layer backbone has no conv 1: its early bucket is final_mlp alone, which is what the library's stage cut leaves final)
-        early_name = "gnn_backbone.module_list.1.lin_query.weight" if self.n_layers > 1 else "final_mlp.0.weight"
+        conv1 = "gnn_backbone.module_list.1." + ("lin.weight" if module.gnn_backbone.arch == "gcn" else "lin_query.weight")
+        early_name = conv1 if self.n_layers > 1 else "final_mlp.0.weight"
         self.early_off = offs[names.index(early_name)]
         self.flat = torch.zeros(self.total, dtype=torch.float32, device=dev)
         self.flat_grad = torch.zeros(self.total, dtype=torch.float32, device=dev)
@@ -148,7 +152,7 @@ class TrainEngine:
     def _weights_struct(self, by):
         w = _lib.DaWeights()
         w.variant = _lib.VARIANT_2D
-        w.arch = _lib.ARCH_EXOPHORMER if self.arch == "exophormer" else _lib.ARCH_TRANSFORMER
+        w.arch = {"exophormer": _lib.ARCH_EXOPHORMER, "gcn": _lib.ARCH_GCN}.get(self.arch, _lib.ARCH_TRANSFORMER)
         w.steps, w.c_in, w.c_out, w.feat_dim, w.hidden = self.steps, self.c_in, self.c_out, self.F, self.hidden
         w.heads, w.n_layers, w.virt_nodes = 8, self.n_layers, self.virt_nodes
         P = lambda n: by[n].data_ptr()  # noqa: E731
@@ -159,6 +163,9 @@ class TrainEngine:
                                                   P("mlp.2.bias"))
         for l in range(self.n_layers):
             p = f"gnn_backbone.module_list.{l}."
+            if self.arch == "gcn":
+                w.conv_wq[l], w.conv_bq[l] = P(p + "lin.weight"), P(p + "bias")
+                continue
             w.conv_wq[l], w.conv_bq[l] = P(p + "lin_query.weight"), P(p + "lin_query.bias")
             w.conv_wk[l], w.conv_bk[l] = P(p + "lin_key.weight"), P(p + "lin_key.bias")
             w.conv_wv[l], w.conv_bv[l] = P(p + "lin_value.weight"), P(p + "lin_value.bias")

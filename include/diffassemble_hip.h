@@ -32,7 +32,8 @@ extern "C" {
 
 enum { DA_PREC_F32 = 0, DA_PREC_BF16 = 1 };
 enum { DA_VARIANT_2D = 0, DA_VARIANT_3D = 1 };          /* Eff_GAT / Eff_GAT_3d            */
-enum { DA_ARCH_TRANSFORMER = 0, DA_ARCH_EXOPHORMER = 1 }; /* GELU between convs / none      */
+enum { DA_ARCH_TRANSFORMER = 0, DA_ARCH_EXOPHORMER = 1, /* GELU between convs / none      */
+       DA_ARCH_GCN = 2 };                                /* two GCNConv, GELU after each    */
 enum { DA_MEAN_EPSILON = 0, DA_MEAN_START_X = 1 };       /* spatial_diffusion.py:63-66      */
 enum { DA_ACT_NONE = 0, DA_ACT_GELU = 1, DA_ACT_LEAKY02 = 2 };
 enum { DA_MAX_LAYERS = 8 };
@@ -80,6 +81,9 @@ int da_build_flags(void);        /* bit 0: EXPERIMENTS build                    
  * (Eff_GAT) or backbones/efficient_gat_3d.py:99-152 (Eff_GAT_3d), incl. the PyG
  * TransformerConv lin_{query,key,value,skip} of backbones/Transformer_GNN.py:9-25 and the
  * virt_node_embedding of backbones/exophormer_gnn.py:158-159.
+ * DA_ARCH_GCN replaces the GCN of backbones/gcn.py:5-22 (efficient_gat.py:65-70, efficient_gat_3d.py:114-119):
+ * n_layers = 2, conv_wq[l] = module_list.l.lin.weight ([256, D] / [D, 256]), conv_bq[l] = module_list.l.bias
+ * ([256] / [D]); the other conv pointers, heads and virt_nodes are not read.
  * ------------------------------------------------------------------------------------- */
 typedef struct da_weights {
     int32_t variant;      /* DA_VARIANT_*                                                  */
@@ -154,7 +158,9 @@ typedef struct da_graph {
      * second kernel merges into the same softmax.  Needs pad_ptr / row_map (virtual rows of a graph get
      * the slots behind its real nodes) and graph_ptr.                                            */
     int32_t hybrid;           /* 0 / 1                                                     */
-    int32_t reserved0;
+    int32_t band_degree;      /* > 0: hybrid graph in the banded Exphander layout of degree d (slot_node set, every
+                               * graph n = max_graph_nodes nodes, no duplicate edges, no virtual rows): the GCN
+                               * aggregates it in closed form (da_gcn.hip).  0 otherwise; the attention ignores it.  */
     const uint8_t *mask;      /* adjacency bits or NULL                                    */
     const int64_t *mask_ptr;  /* [n_graphs + 1] byte offsets                               */
     const int32_t *irr_row_ptr; /* [n_nodes + 1] remainder CSR                             */
@@ -224,6 +230,18 @@ int da_denoiser_set_features(da_denoiser *d, const da_graph *g, const float *fea
 int da_denoiser_forward(da_denoiser *d, const da_graph *g, const float *x, const int64_t *t,
                         int64_t t_scalar, float *out, float *alpha, int alpha_all_layers,
                         float *pre_head, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * GCN aggregation (DA_ARCH_GCN; PyG GCNConv with default settings, backbones/gcn.py:5-22):
+ *   out[n_nodes, W] = act(D^-1/2 (A' + I) D^-1/2 X + bias), A' = the edges without self loops (multi-edges
+ *   counted), degrees at the target.  X / out act dtype, bias fp32 [W] or NULL, W % 4 == 0.  Complete graphs
+ *   (dense != 0) and banded Exphander plans (band_degree > 0) are aggregated in closed form; any other plan needs
+ *   the CSR and dinv [n_nodes] fp32 from da_gcn_dinv (a no-op on the closed-form plans).  Kernel-level test entries;
+ *   da_denoiser_forward runs the same kernels.
+ * ------------------------------------------------------------------------------------- */
+int da_gcn_dinv(const da_graph *g, float *dinv, void *stream);
+int da_gcn_aggregate(int prec, const da_graph *g, int W, const float *dinv, const void *X, const float *bias, int act,
+                     void *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Diffusion schedule tables (fp32 [T] device pointers) == the registered buffers of
@@ -335,6 +353,8 @@ enum {
     DA_PROF_HEAD = 5,         /* pose head                                                   */
     DA_PROF_UPDATE = 6,       /* DDIM / DDPM update                                          */
     DA_PROF_CONV_FUSED = 7,   /* hidden conv as ONE kernel: projection + attention (C = 32)  */
+                              /* DA_ARCH_GCN: its two projections count as LINEAR_QKVS, the aggregation of conv 0
+                               * as ATTN_HIDDEN and that of conv 1 as ATTN_LAST (the classes of the layer's slots)  */
     DA_PROF_NCLASS = 8
 };
 int da_profile_enable(da_denoiser *d, int on);
@@ -413,8 +433,10 @@ int da_debug_counters(int64_t *out /* host [n] */, int n, int reset);
  *   grads  the same struct filled with the gradient pointers (same layout); the library ADDS
  *          into them (zero them per optimizer step).
  *   d_feats nullable [n_real, F]: gradient w.r.t. the piece features, for a trainable encoder.
- * Only the 2D denoiser (arch transformer / exophormer) is implemented; any graph type, through
- * the CSR attention kernels (needs g->out_ptr / g->out_dst).  The forward must precede the
+ * Only the 2D denoiser (arch transformer / exophormer / gcn) is implemented; any graph type, through
+ * the CSR attention kernels (needs g->out_ptr / g->out_dst).  DA_ARCH_GCN: w->conv_wq / conv_bq per layer
+ * (lin.weight, bias) only; complete graphs and banded Exphander plans aggregate in closed form, any other
+ * plan over its CSR (by destination forward, by source -- out_ptr / out_dst -- backward).  The forward must precede the
  * backward on the same workspace, with the same weights: besides the activations it leaves the
  * step's weight images there (W^T of every Linear with a dX product; bf16 copies in the bf16 mode),
  * which the backward reads instead of transposing again.
