@@ -76,7 +76,9 @@ __device__ __forceinline__ u32x4 add_relu8(u32x4 a, u32x4 b, bool relu, bf16_t) 
 // of the LDS and DMA bytes per FLOP, both operands two stages ahead: 352 vs 340 us).  With the DMA compiled out
 // the kernel runs at 1 280 - 1 400 TFLOP/s, which is also what hipBLASLt reaches on this box (1 239): that, not
 // 2.5 PFLOP/s, is the practical ceiling of the matrix pipe here; the DMA stream costs the remaining 25 - 30 %.
-template <typename T>
+// RES: whether the tile has a residual, as a compile-time fact for the bf16 kernel (1 / 0: its two epilogues differ, and
+// the residual-free one then carries no residual registers) and read from p.res by the fp32 kernel (-1).
+template <typename T, int RES>
 __global__ __launch_bounds__(256, 2) void k_conv_mfma(ConvParams p) {
     constexpr int SA = 16384, OFFW = 3 * SA;                 // A ring: 3 x 16 KB, W ring: 2 x 16 KB behind it
     __shared__ __attribute__((aligned(16))) unsigned char smem[5 * SA];
@@ -90,7 +92,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(ConvParams p) {
     const int Ho = 1 << p.lgHo, Wo = 1 << p.lgWo;
     const int K = p.taps * p.Cin;
     const int nk = p.taps << p.lgcpt;
-    const bool relu = p.relu != 0, has_res = p.res != nullptr;
+    const bool relu = p.relu != 0, has_res = RES < 0 ? p.res != nullptr : RES != 0;
     const int lr = lane >> 3, lc = (lane & 7) ^ lr;
 
     // PERSISTENT workgroups: 2 per CU, each walks virtual tiles v, v + grid, ...  A tile's first stage is put in
@@ -224,6 +226,54 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(ConvParams p) {
         // residual is added (and the ReLU applied) on the coalesced side.  Plain barriers: the DMA in flight is
         // the next tile's stage 0, which must NOT be waited for here.
         unsigned char *stg = smem + SA;
+        if (ES == 2 && has_res) {
+            // bf16 maps with a residual: the tile is staged in FP32 (32 rows at a time, the fp32 kernel's layout) and
+            // rounded ONCE, after the residual is added.  Staged in bf16 like the residual-free tile below, the sum was
+            // rounded twice -- conv + bias to bf16, then (that + res) to bf16 -- and missed the correctly rounded
+            // result by up to one more half ulp of the convolution's share (tests/test_gpu_encoder_kernels.py).
+            constexpr int RSF = 128 * 4 + 16, HALVES = ROWS / 32, ITH = NIT / HALVES;
+            static_assert(32 * RSF <= 2 * SA, "fp32 staging lives in A slots 1-2");
+#pragma unroll
+            for (int pass = 0; pass < PASSES; ++pass)
+#pragma unroll
+                for (int h = 0; h < HALVES; ++h) {
+                    if (pass > 0 || h > 0) __syncthreads();
+#pragma unroll
+                    for (int mi = 0; mi < 4; ++mi) {
+#pragma unroll
+                        for (int ni = 0; ni < 4; ++ni) {
+                            const int rg = wm * 64 + mi * 16 + (lane & 15);
+                            if (rg / 32 != pass * HALVES + h) continue;   // wave-uniform
+                            f32x4 vv;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) vv[r] = acc[mi][ni][r] + bz[ni][r];
+                            *(f32x4 *)(stg + (rg % 32) * RSF + (wn * 64 + ni * 16 + (lane >> 4) * 4) * 4) = vv;
+                        }
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int i2 = 0; i2 < ITH; ++i2) {
+                        const int it = h * ITH + i2;
+                        const int idx = tid + it * 256, row = idx / CPR, ch = idx - row * CPR;      // row in [32 h, 32 h + 32)
+                        if (orow0 + row + pass * ROWS >= p.M) continue;
+                        const unsigned char *sp = stg + (row % 32) * RSF + ch * 32;
+                        const f32x4 lo = *(const f32x4 *)sp, hi = *(const f32x4 *)(sp + 16);
+                        const float cv[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                        const u32x4 rr = rv[pass][it];
+                        typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+                        u32x4 val;
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            float a = cv[2 * i] + __builtin_bit_cast(float, rr[i] << 16);
+                            float b = cv[2 * i + 1] + __builtin_bit_cast(float, rr[i] & 0xffff0000u);
+                            if (relu) { a = fmaxf(a, 0.f); b = fmaxf(b, 0.f); }
+                            const bf16x2 pk = {(__bf16)a, (__bf16)b};        // v_cvt_pk_bf16_f32 (round to nearest even)
+                            val[i] = __builtin_bit_cast(unsigned, pk);
+                        }
+                        *(u32x4 *)((T *)p.Y + ooff[pass][it]) = val;
+                    }
+                }
+        } else {
 #pragma unroll
         for (int pass = 0; pass < PASSES; ++pass) {
             if (pass > 0) __syncthreads();
@@ -251,6 +301,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(ConvParams p) {
                 if (has_res) val = add_relu8(val, PREFETCH ? rv[pass][it] : *(const u32x4 *)((const T *)p.res + ooff[pass][it]), relu, T());
                 *(u32x4 *)((T *)p.Y + ooff[pass][it]) = val;
             }
+        }
         }
         if (!more) break;
         v = vn;
@@ -328,8 +379,9 @@ int launch_conv(int prec, int B, const void *X, int Cin, int Hi, const void *W, 
     long long cap = (long long)256 * per_cu / (8 * p.nct) * (8 * p.nct);
     if (cap < 8 * p.nct) cap = 8 * p.nct;
     const unsigned grid = (unsigned)(p.nvirt < cap ? p.nvirt : cap);
-    if (prec == DA_PREC_BF16) k_conv_mfma<bf16_t><<<grid, 256, 0, st>>>(p);
-    else k_conv_mfma<float><<<grid, 256, 0, st>>>(p);
+    if (prec == DA_PREC_BF16 && res) k_conv_mfma<bf16_t, 1><<<grid, 256, 0, st>>>(p);
+    else if (prec == DA_PREC_BF16) k_conv_mfma<bf16_t, 0><<<grid, 256, 0, st>>>(p);
+    else k_conv_mfma<float, -1><<<grid, 256, 0, st>>>(p);
     DA_LAUNCH_CHECK();
     return 0;
 }

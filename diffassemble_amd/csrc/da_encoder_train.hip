@@ -19,7 +19,8 @@
 //     sum may run over ALL haloed positions q, i.e. it is ONE plain TN GEMM per tap on the two maps as they lie in
 //     memory (X shifted by a constant element offset): k_gemm_tn (fp32 MFMA, split over rows), no im2col;
 //   * filter bank -> parameter gradient: every parameter entry feeds exactly 4 bank entries (k_bank_grad, table built once).
-// BatchNorm reductions are two-stage and deterministic (per-block fp32 partials over <= 4096 pixels, summed in double).
+// BatchNorm reductions are two-stage and deterministic: per-block partials over <= 4096 pixels (the statistics' per-thread sums
+// in double, the backward's in fp32), reduced and summed across blocks in double.
 #include "da_internal.h"
 
 namespace da {
@@ -54,9 +55,9 @@ __device__ __forceinline__ size_t pix_off(const MapGeom &g, long long ip) {     
 
 // Block reduction of up to NV values per thread across the block's pixel lanes -> partial[block][plane][NV] (double).
 // 256 threads = (256 / planes) pixel lanes x planes; thread (lane_p, plane) has already summed its pixels.
-template <int NV>
-__device__ __forceinline__ void block_plane_reduce(const float (&v)[NV], int planes, double *partial) {
-    __shared__ float red[256 * NV];
+template <int NV, typename V>
+__device__ __forceinline__ void block_plane_reduce(const V (&v)[NV], int planes, double *partial) {
+    __shared__ V red[256 * NV];
     const int tid = threadIdx.x, plane = tid % planes;
 #pragma unroll
     for (int i = 0; i < NV; ++i) red[i * 256 + tid] = v[i];
@@ -71,17 +72,21 @@ __device__ __forceinline__ void block_plane_reduce(const float (&v)[NV], int pla
     }
 }
 
-// sum and sum of squares per plane over a block's interior pixels
+// sum and sum of squares per plane over a block's interior pixels.  The per-thread sums run in DOUBLE: the variance is
+// E[y^2] - m^2, which for a plane whose mean is 4 standard deviations off zero cancels 17/18 of E[y^2], so an fp32 running sum
+// over a thread's 2 048 values (relative error ~1e-6) left the variance wrong by 3e-5 (tests/test_gpu_encoder_kernels.py).
+// The kernel is bound by its loads; the fp64 adds are free.
 template <typename T>
 __global__ __launch_bounds__(256) void k_enc_bn_stats(MapGeom g, const T *__restrict__ Y, double *__restrict__ partial) {
     const int planes = g.C4 >> 2, lanes = 256 / planes, tid = threadIdx.x, plane = tid % planes, lp = tid / planes;
     const long long total = (long long)g.B * g.H * g.H, p0 = (long long)blockIdx.x * BN_PIX, p1 = min(total, p0 + BN_PIX);
-    float v[2] = {0.f, 0.f};
+    double v[2] = {0.0, 0.0};
 #pragma unroll 4
     for (long long ip = p0 + lp; ip < p1; ip += lanes) {
         const float4 y = ld4(Y, pix_off(g, ip) + 4 * plane);
-        v[0] += (y.x + y.y) + (y.z + y.w);
-        v[1] += (y.x * y.x + y.y * y.y) + (y.z * y.z + y.w * y.w);
+        const double a = y.x, b = y.y, c = y.z, d = y.w;
+        v[0] += (a + b) + (c + d);
+        v[1] += (a * a + b * b) + (c * c + d * d);
     }
     block_plane_reduce<2>(v, planes, partial);
 }
