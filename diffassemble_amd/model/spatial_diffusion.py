@@ -358,14 +358,14 @@ class GNN_Diffusion(LightningModule):
     def configure_optimizers(self):
         """spatial_diffusion.py:701-705: Adafactor with transformers' defaults.  On a ROCm device the denoiser's update
         runs as one library call over the training engine's flat buffers (``FusedAdafactor`` -> da_adafactor_step); with
-        a piece encoder attached its parameters keep transformers' implementation (``HybridAdafactor``).  Set the class / instance
+        a piece encoder attached its parameters take a second library call (``HybridAdafactor`` -> ``FusedAdafactorND`` -> da_adafactor_nd_step).  Set the class / instance
         attribute ``fused_optimizer = False`` for transformers' own implementation throughout."""
         fused = bool(getattr(self, "fused_optimizer", True))
         if fused and self.device.type == "cuda" and getattr(self.model, "visual_backbone", None) is None:
             from ..train import FusedAdafactor
             return FusedAdafactor(self.parameters(), self.model.train_engine(self.device))
         if fused and self.device.type == "cuda":
-            # trainable piece encoder attached: fused update for the denoiser, transformers' Adafactor (same rule) for the rest
+            # trainable piece encoder attached: fused update for the denoiser's flat buffer, FusedAdafactorND (same rule, by pointer) for the rest
             from ..train import HybridAdafactor
             return HybridAdafactor(self.parameters(), self.model.train_engine(self.device))
         from transformers.optimization import Adafactor

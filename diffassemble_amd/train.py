@@ -457,22 +457,261 @@ class FusedAdafactor(torch.optim.Optimizer):
         return loss
 
 
+ND_TILE_ROWS, ND_TILE_COLS, ND_VEC_BLOCK, ND_COL_JOB, ND_TINY_SLICE, ND_SLICES_PER_BLOCK = 16, 1024, 4096, 64, 64, 256   # da_optim_nd.hip
+ND_KIND_VECTOR, ND_KIND_TINY, ND_KIND_TILED = 0, 1, 2
+
+
+class AdafactorNDPlan:
+    """The tables of ``da_adafactor_nd_step`` for a list of tensor shapes (no device, no pointers: a pure function of the
+    shapes, tests/test_adafactor_nd_host.py).  ``tensors[i]``: kind, B, R, C, the offsets and sizes of its statistics in the
+    state buffer (``row_off`` / ``row_size`` = transformers' ``exp_avg_sq_row`` flattened -- or ``exp_avg_sq`` for rank <= 1 --
+    and ``col_off`` / ``col_size`` = ``exp_avg_sq_col``), its block range and scratch offsets.  ``blocks`` [n, 6] int32
+    (pid, b, r0, nr, c0, nc) and ``jobs`` [m, 3] int32 (pid, b, c0) as include/diffassemble_hip.h describes them."""
+
+    def __init__(self, shapes):
+        import numpy as np
+        self.tensors, blocks, jobs = [], [], []
+        s_off = cp_off = rp_off = n_slices = 0
+        for pid, shape in enumerate(shapes):
+            shape = tuple(int(d) for d in shape)
+            numel = 1
+            for d in shape:
+                numel *= d
+            if numel <= 0 or numel >= 2 ** 31:
+                raise _lib.DaError(f"FusedAdafactorND: parameter {pid} of shape {shape} has {numel} elements (1 .. 2^31 - 1 supported)")
+            t = dict(shape=shape, numel=numel, blk0=len(blocks), colpart_off=0, rowpart_off=0, rmean_off=0)
+            if len(shape) < 2:
+                t.update(kind=ND_KIND_VECTOR, B=1, R=1, C=numel, row_off=s_off, row_size=numel, col_off=0, col_size=0)
+                s_off += numel
+                blocks += [(pid, 0, e0, min(ND_VEC_BLOCK, numel - e0), 0, 0) for e0 in range(0, numel, ND_VEC_BLOCK)]
+                jobs.append((pid, 0, -1))
+            else:
+                R, C = shape[-2:]
+                B = numel // (R * C)
+                t.update(B=B, R=R, C=C, row_off=s_off, row_size=B * R, col_off=s_off + B * R, col_size=B * C)
+                s_off += B * (R + C)
+                if R * C <= ND_TINY_SLICE:
+                    t["kind"] = ND_KIND_TINY
+                    blocks += [(pid, 0, s0, min(ND_SLICES_PER_BLOCK, B - s0), 0, 0) for s0 in range(0, B, ND_SLICES_PER_BLOCK)]
+                    jobs.append((pid, 0, -1))
+                else:
+                    nrb, ncb = -(-R // ND_TILE_ROWS), -(-C // ND_TILE_COLS)
+                    t.update(kind=ND_KIND_TILED, colpart_off=cp_off, rowpart_off=rp_off, rmean_off=n_slices)
+                    cp_off += B * nrb * C
+                    rp_off += B * ncb * R
+                    n_slices += B
+                    for b in range(B):
+                        blocks += [(pid, b, r0, min(ND_TILE_ROWS, R - r0), c0, min(ND_TILE_COLS, C - c0))
+                                   for r0 in range(0, R, ND_TILE_ROWS) for c0 in range(0, C, ND_TILE_COLS)]
+                        jobs.append((pid, b, -1))
+                        jobs += [(pid, b, c0) for c0 in range(0, C, ND_COL_JOB)]
+            t["nblk"] = len(blocks) - t["blk0"]
+            self.tensors.append(t)
+        self.blocks = np.asarray(blocks, dtype=np.int32).reshape(-1, 6)
+        self.jobs = np.asarray(jobs, dtype=np.int32).reshape(-1, 3)
+        self.state_floats, self.n_slices, self.colpart_floats, self.rowpart_floats = s_off, n_slices, cp_off, rp_off
+        self.scal_off = 2 * len(blocks)                 # scratch: p^2 partials | u^2 partials | [n][4] scalars | row means | colpart | rowpart
+        self.scratch_floats = 2 * len(blocks) + 4 * len(self.tensors) + n_slices + cp_off + rp_off
+
+    def param_table(self):
+        """The 80-byte records with null pointers and ``active`` = 0 (numpy structured array; ``FusedAdafactorND`` fills p, g, active)."""
+        import numpy as np
+        dt = np.dtype([(k, "<i8") for k in ("p", "g", "row_off", "col_off", "colpart_off", "rowpart_off")]
+                      + [(k, "<i4") for k in ("B", "R", "C", "kind", "blk0", "nblk", "active", "rmean_off")])
+        tab = np.zeros(len(self.tensors), dtype=dt)
+        for i, t in enumerate(self.tensors):
+            for k in dt.names:
+                if k in t:
+                    tab[i][k] = t[k]
+        return tab
+
+
+def _check_nd_tensor(what, i, t, device=None):
+    """fp32, contiguous, on a GPU (and on ``device``): the kernels address it by raw pointer."""
+    where = f"FusedAdafactorND: {what} {i} (shape {tuple(t.shape)})"
+    if t.dtype != torch.float32:
+        raise _lib.DaError(f"{where} is {t.dtype}, not torch.float32")
+    if not t.is_contiguous():
+        raise _lib.DaError(f"{where} is not contiguous")
+    if device is not None and (t.device.type != "cuda" or (device.type == "cuda" and t.device != device)):
+        raise _lib.DaError(f"{where} is on {t.device}, not on " + (str(device) if device.type == "cuda" else "a GPU"))
+
+
+class FusedAdafactorND(torch.optim.Optimizer):
+    """The reference's optimizer (``Adafactor(self.parameters())`` with transformers' defaults, spatial_diffusion.py:701-705)
+    for an ARBITRARY list of fp32, contiguous, same-device parameters of any rank, as ONE library call
+    (``da_adafactor_nd_step``: four launches whatever the number of tensors, deterministic reductions, no host sync).  The
+    tensors are addressed by pointer: the piece encoder's and the fragment encoder's parameters are separate allocations,
+    their gradients views of a flat buffer or plain ``.grad`` tensors.  The tables are built once; the parameter table is
+    uploaded again only when a parameter's or a gradient's address, a gradient's layout or the set of parameters that have one
+    changes (compared on the host).  Slices of more than 64 elements take the tiled path, one workgroup per slice and 16 x 1024
+    tile: right for matrices, wasteful for a bank of MANY medium slices (a 7x7 filter bank, [Co, Ci, 9, 8]) -- correct, but one
+    small workgroup per slice; neither encoder has such a tensor.  A
+    parameter without a gradient is skipped and keeps its own step count, as transformers does.  After the update the
+    parameters' version counters are bumped (the encoders' packed-weight caches key on them).  ``state_dict`` /
+    ``load_state_dict`` use transformers' per-parameter layout, so checkpoints move between the two classes.
+    First moment, weight decay, an external learning rate and warm-up initialisation (never used by the reference) raise."""
+
+    def __init__(self, params, eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, lr=None, beta1=None, weight_decay=0.0,
+                 scale_parameter=True, relative_step=True, warmup_init=False):
+        import numpy as np
+        params = list(params)
+        defaults = dict(lr=lr, eps=tuple(eps), clip_threshold=clip_threshold, decay_rate=decay_rate, beta1=beta1, weight_decay=weight_decay,
+                        scale_parameter=scale_parameter, relative_step=relative_step, warmup_init=warmup_init)   # transformers' keys
+        flat = [q for g in params for q in g["params"]] if params and isinstance(params[0], dict) else params
+        elsewhere = None
+        for i, p in enumerate(flat):                      # one pass; dtype / layout first, so the message names the first thing wrong
+            _check_nd_tensor("parameter", i, p)
+            if elsewhere is None and (p.device.type != "cuda" or p.device != flat[0].device):
+                elsewhere = i
+        if elsewhere is not None:
+            _check_nd_tensor("parameter", elsewhere, flat[elsewhere], flat[0].device)
+        super().__init__(params, defaults)
+        self._check_groups(self.param_groups)
+        self._params = [p for g in self.param_groups for p in g["params"]]
+        self.device = dev = self._params[0].device
+        self.lib = _lib.lib()
+        self.plan = plan = AdafactorNDPlan([p.shape for p in self._params])
+        self._host_tab = plan.param_table()
+        self._sig = None                                       # per parameter (its address, its gradient's address / dtype / strides), as last uploaded
+        self._steps = [0] * len(self._params)                  # host mirror of steps_dev (no device read on the way)
+        self.ptab = torch.zeros(self._host_tab.nbytes // 8, dtype=torch.int64, device=dev)
+        self.btab = torch.from_numpy(plan.blocks.reshape(-1)).to(dev)
+        self.jtab = torch.from_numpy(plan.jobs.reshape(-1)).to(dev)
+        self.steps_dev = torch.zeros(len(self._params), dtype=torch.int32, device=dev)
+        self.state_buf = torch.zeros(max(plan.state_floats, 1), dtype=torch.float32, device=dev)
+        self.scratch = torch.zeros(plan.scratch_floats + 64, dtype=torch.float32, device=dev)
+        self._np = np
+
+    @staticmethod
+    def _check_groups(groups):
+        for g in groups:
+            if g.get("beta1") is not None or g.get("weight_decay", 0.0) != 0.0 or g.get("lr") is not None \
+                    or not g.get("relative_step", True) or not g.get("scale_parameter", True) or g.get("warmup_init", False):
+                raise NotImplementedError("FusedAdafactorND implements the reference's configuration only: relative step, scale_parameter, "
+                                          "no first moment (beta1), no weight decay, no external lr, no warmup_init")
+        hyper = {(tuple(g["eps"]), g["clip_threshold"], g["decay_rate"]) for g in groups}
+        if len(hyper) > 1:
+            raise NotImplementedError(f"FusedAdafactorND: one set of (eps, clip_threshold, decay_rate) for all groups, got {sorted(hyper)}")
+
+    # ------------------------------------------------------------------ checkpoint / resume (transformers' layout)
+    def state_dict(self):
+        """``{"state": {index: {"step", "exp_avg_sq_row" [shape[:-1]], "exp_avg_sq_col" [shape[:-2] + shape[-1:]] | "exp_avg_sq",
+        "RMS" (0-dim)}}, "param_groups"}`` -- what ``transformers.optimization.Adafactor(...).state_dict()`` holds over the same
+        parameter list; a parameter that never had a gradient has no entry, as there."""
+        sd = super().state_dict()
+        state = {}
+        for i, (p, t) in enumerate(zip(self._params, self.plan.tensors)):
+            if self._steps[i] == 0:
+                continue
+            st = {"step": self._steps[i]}
+            ro, co = t["row_off"], t["col_off"]
+            if t["kind"] == ND_KIND_VECTOR:
+                st["exp_avg_sq"] = self.state_buf[ro:ro + t["row_size"]].clone().view(p.shape)
+            else:
+                st["exp_avg_sq_row"] = self.state_buf[ro:ro + t["row_size"]].clone().view(p.shape[:-1])
+                st["exp_avg_sq_col"] = self.state_buf[co:co + t["col_size"]].clone().view(p.shape[:-2] + p.shape[-1:])
+            st["RMS"] = self.scratch[self.plan.scal_off + 4 * i + 1].clone()
+            state[i] = st
+        sd["state"] = state
+        return sd
+
+    def load_state_dict(self, sd):
+        groups = sd.get("param_groups")
+        if groups is not None:
+            if len(groups) != len(self.param_groups) or any(len(a["params"]) != len(b["params"]) for a, b in zip(groups, self.param_groups)):
+                raise ValueError("FusedAdafactorND.load_state_dict: the parameter groups do not match this optimizer's")
+            self._check_groups(groups)
+            for mine, theirs in zip(self.param_groups, groups):
+                mine.update({k: (tuple(v) if k == "eps" else v) for k, v in theirs.items() if k != "params"})
+        state = sd.get("state", {})
+        with torch.no_grad():
+            for i, (p, t) in enumerate(zip(self._params, self.plan.tensors)):
+                st = state.get(i, state.get(str(i)))
+                ro, co = t["row_off"], t["col_off"]
+                row, col = self.state_buf[ro:ro + t["row_size"]], self.state_buf[co:co + t["col_size"]]
+                if not st:
+                    self._steps[i] = 0
+                    row.zero_()
+                    col.zero_()
+                    continue
+                self._steps[i] = int(st["step"])
+                if t["kind"] == ND_KIND_VECTOR:
+                    row.copy_(st["exp_avg_sq"].reshape(-1))
+                else:
+                    row.copy_(st["exp_avg_sq_row"].reshape(-1))
+                    col.copy_(st["exp_avg_sq_col"].reshape(-1))
+                if torch.is_tensor(st.get("RMS")):
+                    self.scratch[self.plan.scal_off + 4 * i + 1].copy_(st["RMS"].reshape(()))
+            self.steps_dev.copy_(torch.tensor(self._steps, dtype=torch.int32))
+
+    def _upload(self, sig):
+        for i, (p, a) in enumerate(zip(self._params, sig)):
+            _check_nd_tensor("parameter", i, p, self.device)       # (its storage may have been replaced since construction)
+            if tuple(p.shape) != self.plan.tensors[i]["shape"]:
+                raise _lib.DaError(f"FusedAdafactorND: parameter {i} changed shape from {self.plan.tensors[i]['shape']} to {tuple(p.shape)}")
+            if a[1]:
+                _check_nd_tensor("the gradient of parameter", i, p.grad, self.device)
+                if p.grad.shape != p.shape:
+                    raise _lib.DaError(f"FusedAdafactorND: the gradient of parameter {i} has shape {tuple(p.grad.shape)}, not {tuple(p.shape)}")
+        self._host_tab["p"] = [a[0] for a in sig]
+        self._host_tab["g"] = [a[1] for a in sig]
+        self._host_tab["active"] = [1 if a[1] else 0 for a in sig]
+        self.ptab.copy_(torch.from_numpy(self._host_tab.view(self._np.int64).reshape(-1)))
+        self._sig = sig
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        # every raw address the kernels will use, and the gradients' layout, compared on the host: a parameter whose storage was
+        # replaced (module.to(...), p.data = ...) or a gradient that moved / changed layout is seen here, checked and uploaded again
+        sig = tuple((p.data_ptr(), 0) if p.grad is None else (p.data_ptr(), p.grad.data_ptr(), p.grad.dtype, p.grad.stride())
+                    for p in self._params)
+        if not any(a[1] for a in sig):
+            return loss                                   # nothing back-propagated yet
+        if sig != self._sig:
+            self._upload(sig)
+        g = self.param_groups[0]
+        plan = self.plan
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.da_adafactor_nd_step(
+                len(self._params), _lib.ptr(self.ptab), len(plan.blocks), _lib.ptr(self.btab), len(plan.jobs), _lib.ptr(self.jtab),
+                _lib.ptr(self.steps_dev), _lib.ptr(self.state_buf), _lib.ptr(self.scratch), self.scratch.numel(), plan.n_slices,
+                plan.colpart_floats, plan.rowpart_floats, g["eps"][0], g["eps"][1], g["clip_threshold"], g["decay_rate"], _lib.stream_ptr(self.device)))
+        updated = []
+        for i, a in enumerate(sig):
+            if a[1]:
+                self._steps[i] += 1
+                updated.append(self._params[i])
+        torch.autograd.graph.increment_version(updated)    # the raw-pointer update is invisible to autograd / the packed-weight caches
+        return loss
+
+
 class HybridAdafactor(torch.optim.Optimizer):
     """The reference's single ``Adafactor(self.parameters())`` (spatial_diffusion.py:701-705) when a trainable piece
     encoder is attached: the denoiser's parameters go through ``FusedAdafactor`` (one library call over the flat buffers),
-    every other parameter with a gradient (the encoder's 5-D group-convolution weights, BatchNorm affines, the two wide
-    linears -- shapes the fused kernel's row / column tables do not cover) through transformers' own Adafactor with the
-    same defaults, so the update rule is the reference's for all of them.  Presents itself as ONE optimizer (Lightning's
-    automatic optimisation wants exactly one)."""
+    every other trainable parameter (the encoder's 5-D group-convolution weights, BatchNorm affines, the two wide
+    linears) through ``FusedAdafactorND`` (a second library call, tensors addressed by pointer): two calls, eight launches, no
+    host sync for the whole model.  ``fused_rest=False`` hands the second half to transformers' own Adafactor with the same
+    defaults instead (the route before da_adafactor_nd_step existed: A/B timing, escape hatch); the checkpoint layout is the
+    same either way.  Presents itself as ONE optimizer (Lightning's automatic optimisation wants exactly one)."""
 
-    def __init__(self, params, engine: TrainEngine):
-        from transformers.optimization import Adafactor
+    def __init__(self, params, engine: TrainEngine, fused_rest=True):
         params = list(params)
         mine = {id(p) for p in engine.params}
         rest = [p for p in params if id(p) not in mine and p.requires_grad]
         super().__init__(params, {})
         self.fused = FusedAdafactor([p for p in params if id(p) in mine], engine)
-        self.rest = Adafactor(rest) if rest else None
+        if not rest:
+            self.rest = None
+        elif fused_rest:
+            self.rest = FusedAdafactorND(rest)
+        else:
+            from transformers.optimization import Adafactor
+            self.rest = Adafactor(rest)
 
     def zero_grad(self, set_to_none: bool = True):
         self.fused.zero_grad(set_to_none)

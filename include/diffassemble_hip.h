@@ -515,6 +515,39 @@ int da_adafactor_step(int n_params, const void *param_table, int n_blocks, const
                       float decay_rate, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Fused Adafactor step for any list of fp32 tensors of any rank, addressed by pointer (added under
+ * ABI 19, backwards-compatible; one call = one optimizer step for every ACTIVE tensor, 4 launches
+ * whatever their number, deterministic two-stage reductions, no host sync).  Replaces, for every
+ * trainable tensor outside the flat buffers above (the piece encoder's 5-D group-convolution banks,
+ * BatchNorm affines, linear1 / linear2; the fragment encoder), the same
+ * transformers.optimization.Adafactor(self.parameters()) of spatial_diffusion.py:701-705, including
+ * its treatment of a tensor [..., R, C] as prod(shape[:-2]) independent [R, C] slices for the
+ * factored second moment, rms(p) / rms(u) over the whole tensor, and a step count PER tensor that
+ * advances only when the tensor has a gradient.
+ *   param_table  device array of n_params records {float *p; const float *g; int64 row_off, col_off,
+ *                colpart_off, rowpart_off; int32 B, R, C, kind, blk0, nblk, active, rmean_off}
+ *                (80 bytes).  kind 0 = unfactored (rank <= 1: B = R = 1, C = numel, v at row_off),
+ *                1 = tiny slices (R C <= 64, one lane per slice), 2 = tiles of 16 rows x 1024 columns.
+ *                State: row[B][R] at row_off, col[B][C] at col_off (transformers' exp_avg_sq_row /
+ *                exp_avg_sq_col, flattened).  active = 0: the tensor is skipped this step.
+ *   block_table  device array of n_blocks records {int32 pid, b, r0, nr, c0, nc}   (24 bytes):
+ *                kind 0: nr <= 4096 elements from r0; kind 1: nr <= 256 slices from slice r0;
+ *                kind 2: rows r0 .. r0+nr (r0 a multiple of 16, nr <= 16) x columns c0 .. c0+nc
+ *                (c0 a multiple of 1024, nc <= 1024) of slice b.  A tensor's blocks are contiguous.
+ *   job_table    device array of n_jobs records {int32 pid, b, c0}                 (12 bytes):
+ *                c0 < 0: the row statistics of slice b (every tensor has the job b = 0, which also
+ *                computes its learning rate); c0 >= 0 (kind 2): the 64 columns from c0 of slice b.
+ *   steps        [n_params] int32 step counts, advanced here for the active tensors
+ *   scratch      >= 2*n_blocks + 4*n_params + n_slices + colpart_floats + rowpart_floats, where
+ *                kind-2 tensors own colpart[B][ceil(R/16)][C] and rowpart[B][ceil(C/1024)][R];
+ *                scratch[2*n_blocks + 4*pid + 1] holds rms(p) of the last step (transformers' "RMS").
+ * ------------------------------------------------------------------------------------- */
+int da_adafactor_nd_step(int n_params, const void *param_table, int n_blocks, const void *block_table,
+                         int n_jobs, const void *job_table, int *steps, float *state, float *scratch,
+                         size_t scratch_floats, int n_slices, size_t colpart_floats, size_t rowpart_floats,
+                         float eps1, float eps2, float clip_threshold, float decay_rate, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Greedy assignment of predicted positions to grid cells, one workgroup per puzzle, no host sync.
  * Replaces greedy_cost_assignment (spatial_diffusion.py:179-216) as called by validation_step /
  * test_step (:931-955).  Puzzle g owns rows ptr1[g]..ptr1[g+1] of pos1 (row stride ld1 floats, x
