@@ -99,6 +99,7 @@ class DaPcdEncoderWeights(C.Structure):
     ]
 
 
+LOSS3D_TRANS, LOSS3D_SHAPE_CD, LOSS3D_ROT, LOSS3D_ALL = 1, 2, 4, 7
 PCD_TRAIN_LAYERS = 8      # conv1..conv6, VnInv.vn1, VnInv.vn2
 
 
@@ -204,6 +205,10 @@ PROTOTYPES = {
                                         C.POINTER(DaPcdTrainGrads), _fp, C.c_size_t, C.c_int, _fp]),
     "da_knn": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp]),
     "da_nearest_sq": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
+    "da_loss3d_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "da_loss3d_forward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_float, C.c_float, C.c_float, _fp, _fp, _fp,
+                                    _fp, C.c_size_t, _fp]),
+    "da_loss3d_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
     "da_enc_train_scratch_bytes": (C.c_size_t, [C.c_int]),
     "da_enc_conv": (C.c_int, [C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "da_enc_stem": (C.c_int, [C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp]),

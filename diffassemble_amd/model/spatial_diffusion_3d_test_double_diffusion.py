@@ -171,6 +171,14 @@ class GNN_Diffusion(LightningModule):
     def p_sample(self, x, t, t_index, edge_index, sampling_func, pcd_feats, batch):
         return sampling_func(x, t, t_index, edge_index, pcd_feats, batch)
 
+    def pose_losses(self, prediction, target, cond, n_batch, valids, loss_type="all"):
+        """The loss of ...double_diffusion.py:462-572 behind the noising and the forward: prediction / target [P, 7] (quaternion
+        wxyz | translation), cond [P, N, 3] the fragments -> the weighted ``loss_dict`` (diffassemble_amd/losses3d.py; HIP
+        forward and backward, the gradient reaches ``prediction``).  The seam a later ``p_losses`` calls.  ``valids`` must
+        mark exactly P slots; that is not checked on the device (no host synchronisation), see ``assembly_losses``."""
+        from .. import losses3d
+        return losses3d.assembly_losses(prediction, target, cond, n_batch, valids, n_parts=self.max_num_part, loss_type=loss_type)
+
     def p_losses(self, *args, **kwargs):
         raise NotImplementedError("3D training losses (pytorch3d kNN / chamfer) are out of scope: SURVEY.md 2 #2")
 

@@ -697,6 +697,34 @@ int da_pcd_train_backward(const da_pcd_train_weights *w, int n_parts, int n_poin
 int da_nearest_sq(int n_clouds, int n, int m, const float *a, const float *b, float *d_ab, float *d_ba, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The 3D assembly losses of loss_type="all" (model/utils_3d.py:585-890 as called at
+ * spatial_diffusion_3d_test_double_diffusion.py:500-562): trans_l2_loss, shape_cd_loss and rot_cosine_loss per shape,
+ * and the gradient with respect to the predicted poses.  pts [n_pieces, n_points, 3] (the fragments' own clouds),
+ * pred / gt [n_pieces, 7] (quaternion wxyz | translation), piece_map int32 [n_pieces][2] = (shape, slot): the pieces of
+ * one shape are consecutive rows with ascending slots, slots 0 .. n_parts - 1 (n_parts <= 64), slots without a piece are
+ * the padded parts.  Quaternions go through Rotation3D._process_zero_quat (norm <= 0.5 -> identity, no gradient) and
+ * are applied as pytorch3d quaternion_apply does, without normalisation.  The poses are applied inside the kernels;
+ * padded parts are not searched: they enter as the single candidate (1e3, 1e3, 1e3).
+ * `terms`: which losses to compute (the others read 0); the shape term alone needs pts / dist / idx.
+ * No allocation, no synchronisation, every launch on `stream`; no floating-point atomics: bitwise reproducible.
+ * ------------------------------------------------------------------------------------- */
+enum { DA_LOSS3D_TRANS = 1, DA_LOSS3D_SHAPE_CD = 2, DA_LOSS3D_ROT = 4, DA_LOSS3D_ALL = 7 };
+size_t da_loss3d_workspace_bytes(int n_batch, int n_parts, int n_points);
+/* dist / idx [2][n_pieces, n_points]: for every point of every piece, the squared distance to the nearest point of the
+ * other shape and that point's index slot * n_points + point (ties: lowest index); [0] predicted -> target, [1] target ->
+ * predicted.  out [3][n_batch] = trans_l2_loss, shape_cd_loss, rot_cosine_loss per shape, then out[3 n_batch + k] =
+ * weight k x the mean of row k over the shapes (3 n_batch + 3 floats; w_trans, w_shape_cd, w_rot: the loss weights).  Sums
+ * run in fp64 in a fixed order, each output is rounded once.  The workspace is read again by the backward. */
+int da_loss3d_forward(int n_pieces, int n_points, int n_batch, int n_parts, int terms, const float *pts, const float *pred,
+                      const float *gt, const int32_t *piece_map, float w_trans, float w_shape_cd, float w_rot, float *dist,
+                      int32_t *idx, float *out, void *workspace, size_t workspace_bytes, void *stream);
+/* grad_out [3][n_batch] (gradient of the per-shape rows of `out`) -> grad_pred [n_pieces, 7] (overwritten); idx and the
+ * workspace as the forward of the same inputs left them.  The target receives no gradient, as in the reference. */
+int da_loss3d_backward(int n_pieces, int n_points, int n_batch, int n_parts, int terms, const float *pts, const float *pred,
+                       const float *gt, const int32_t *piece_map, const int32_t *idx, const float *grad_out, float *grad_pred,
+                       const void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Training path of the 2D piece encoder (the encoder runs in EVERY training step,
  * model/spatial_diffusion.py:450): fp32 primitives over the zero-haloed NHWC maps [B][H+2][H+2][C4]
  * (C4 = planes * 4, channel = plane * 4 + rotation; the halo must be zero and is never written).  Together
