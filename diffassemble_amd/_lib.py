@@ -122,6 +122,33 @@ class DaPcdTrainGrads(C.Structure):
     ]
 
 
+# passes of da_pcd_train_pass (include/diffassemble_hip.h, "Passes of the 3D encoder's training path"), enum order
+PCD_PASSES = ("PREMAP", "EDGE_STAT_A", "EDGE_STAT_B", "EDGE_BWD1", "EDGE_BWD2", "EDGE_BWD3", "C6_STAT", "C6_BWD1", "C6_BWD2", "C6_DX",
+              "BN_FIN_FWD", "BN_FIN_BWD", "REV_ADJ", "GATHER", "PREMAP_WGRAD", "HEAD_BWD", "LIN0_GRAD", "VN_LIN", "VN_STAT", "VN_APPLY")
+PCD_PASS = {n: i for i, n in enumerate(PCD_PASSES)}
+
+
+class DaPcdPassArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("n_parts", "n_points", "cin", "feat", "has_b", "inv", "channels", "nblk", "ld_x", "ld_g", "ld_m",
+                                         "vn_cin")]
+                + [("count", C.c_double), ("momentum", C.c_float), ("eps", C.c_float)]
+                + [(n, _fp) for n in ("x", "w", "w2", "T", "idx", "rec_a", "rec_b", "dX_in", "partial", "Gb", "Hb", "E", "X1", "X2", "X3", "dm_in",
+                                      "G6", "F", "dX1", "dX2", "dX3", "gamma", "beta", "running_mean", "running_var", "run_out", "ss",
+                                      "dgamma", "dbeta", "cnt", "ptr", "cur", "rev", "dXp", "dTc", "Xc", "dWm", "dwf", "dwd", "grad_out",
+                                      "dm", "vP", "vD", "vY")])
+
+
+def pcd_train_pass(name, stream=None, **fields):
+    """Run one pass of the 3D encoder's training path (da_pcd_train_pass): tensors become device pointers, the rest plain fields."""
+    a = DaPcdPassArgs()
+    keys = dict(DaPcdPassArgs._fields_)
+    for k, v in fields.items():
+        if k not in keys:
+            raise DaError(f"da_pcd_pass_args has no field {k!r}")
+        setattr(a, k, v.data_ptr() if torch.is_tensor(v) else v)
+    check(lib().da_pcd_train_pass(PCD_PASS[name], C.byref(a), stream if stream is not None else stream_ptr()))
+
+
 class DaConfig(C.Structure):
     """include/diffassemble_hip.h `da_config`: the library's switches (one environment variable each, settable at run time)."""
     _fields_ = [(n, C.c_int32) for n in ("struct_bytes", "disable_mfma", "disable_dense", "disable_folds", "attn_level", "xpanel", "tail_next",
@@ -203,6 +230,7 @@ PROTOTYPES = {
                                        C.c_size_t, _fp, C.c_size_t, _fp]),
     "da_pcd_train_backward": (C.c_int, [C.POINTER(DaPcdTrainWeights), C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp,
                                         C.POINTER(DaPcdTrainGrads), _fp, C.c_size_t, C.c_int, _fp]),
+    "da_pcd_train_pass": (C.c_int, [C.c_int, C.POINTER(DaPcdPassArgs), _fp]),
     "da_knn": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp]),
     "da_nearest_sq": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
     "da_loss3d_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -660,6 +660,116 @@ int check_weights(const da_pcd_train_weights *w, int P, int N, int inv) {
     return 0;
 }
 
+// ---- launches: one helper per pass, shared by da_pcd_train_forward / _backward and by da_pcd_train_pass -------------------
+int edge_launch(int mode, bool hb, const EdgeArgs &a, hipStream_t st) {
+    const int nb = (int)((a.npts + 255) / 256);
+    switch (mode) {
+    case M_STAT_A:
+        if (hb) k_pt_edge<M_STAT_A, true><<<nb, 256, 0, st>>>(a);
+        else k_pt_edge<M_STAT_A, false><<<nb, 256, 0, st>>>(a);
+        break;
+    case M_STAT_B:
+        DA_REQUIRE(hb, "da_pcd_train: the statistics of layer b need a layer b");
+        k_pt_edge<M_STAT_B, true><<<nb, 256, 0, st>>>(a);
+        break;
+    case M_BWD1:
+        if (hb) k_pt_edge<M_BWD1, true><<<nb, 256, 0, st>>>(a);
+        else k_pt_edge<M_BWD1, false><<<nb, 256, 0, st>>>(a);
+        break;
+    case M_BWD2:
+        DA_REQUIRE(hb, "da_pcd_train: the second backward pass needs a layer b");
+        k_pt_edge<M_BWD2, true><<<nb, 256, 0, st>>>(a);
+        break;
+    case M_BWD3:
+        if (hb) k_pt_edge<M_BWD3, true><<<nb, 256, 0, st>>>(a);
+        else k_pt_edge<M_BWD3, false><<<nb, 256, 0, st>>>(a);
+        break;
+    default:
+        DA_REQUIRE(false, "da_pcd_train: unknown edge pass %d", mode);
+    }
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int c6_launch(int mode, const float *X1, const float *X2, const float *X3, const float *w6, int feat, int N, long long npts,
+              const float *rec, const float *dm, double *partial, float *G6, int g6ld, float *F, hipStream_t st) {
+    const int nb = (int)((npts + 255) / 256);
+    if (mode == C6_STAT) k_c6<C6_STAT><<<nb, 256, 0, st>>>(X1, X2, X3, w6, feat, N, npts, rec, dm, partial, G6, g6ld, F);
+    else if (mode == C6_BWD1) k_c6<C6_BWD1><<<nb, 256, 0, st>>>(X1, X2, X3, w6, feat, N, npts, rec, dm, partial, G6, g6ld, F);
+    else k_c6<C6_BWD2><<<nb, 256, 0, st>>>(X1, X2, X3, w6, feat, N, npts, rec, dm, partial, G6, g6ld, F);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int c6_dx_launch(const float *G6, int g6ld, const float *w6, int feat, long long rows, float *dX1, float *dX2, float *dX3,
+                 hipStream_t st) {
+    k_c6_dx<<<(unsigned)((rows + 255) / 256), 256, 0, st>>>(G6, g6ld, w6, feat, rows, dX1, dX2, dX3);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int bn_fin_fwd_launch(const double *partial, int nb, int C, double count, const float *gamma, const float *beta, float mom, float eps,
+                      const float *rm, const float *rv, float *rec, float *run_out, float *ss, int ss_ld, hipStream_t st) {
+    k_bn_fin_fwd<<<C, 256, 0, st>>>(partial, nb, C, count, gamma, beta, mom, eps, rm, rv, rec, run_out, ss, ss_ld);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int bn_fin_bwd_launch(const double *partial, int nb, int C, double count, float *rec, float *dgamma, float *dbeta, hipStream_t st) {
+    k_bn_fin_bwd<<<C, 256, 0, st>>>(partial, nb, C, count, rec, dgamma, dbeta);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+// reverse adjacency of B clouds of N points: cnt, ptr [B N], rev [B N 20]; cur [B N]: the fill's cursors (scratch)
+int rev_adj_launch(int B, int N, const int32_t *idx, int32_t *cnt, int32_t *ptr, int32_t *cur, int32_t *rev, hipStream_t st) {
+    const long long cp = (long long)B * N, ne = cp * KNN;
+    const unsigned ge = (unsigned)((ne + 255) / 256);
+    DA_CHECK_HIP(hipMemsetAsync(cnt, 0, (size_t)cp * 4, st));
+    k_rev_count<<<ge, 256, 0, st>>>(ne, N, idx, cnt);
+    DA_LAUNCH_CHECK();
+    k_rev_scan<<<B, 256, 0, st>>>(N, cnt, ptr, cur);
+    DA_LAUNCH_CHECK();
+    k_rev_fill<<<ge, 256, 0, st>>>(ne, N, idx, cur, rev);
+    DA_LAUNCH_CHECK();
+    k_rev_sort<<<(int)((cp + 255) / 256), 256, 0, st>>>(cp, ptr, cnt, rev);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int gather_launch(int C, long long cp, const float *E, const int32_t *ptr, const int32_t *cnt, const int32_t *rev, const float *Wm,
+                  const float *X, int ldx, float *dXp, float *dTc, float *Xc, hipStream_t st) {
+    const int nb = (int)((cp + 255) / 256);
+    if (C == 1) k_gather<1><<<nb, 256, 0, st>>>(cp, E, ptr, cnt, rev, Wm, X, ldx, dXp, dTc, Xc);
+    else k_gather<VC><<<nb, 256, 0, st>>>(cp, E, ptr, cnt, rev, Wm, X, ldx, dXp, dTc, Xc);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int premap_wgrad_launch(int C, const float *dWm, float *dwf, float *dwd, hipStream_t st) {
+    k_premap_wgrad<<<(VC * C + 255) / 256, 256, 0, st>>>(C, dWm, dwf, dwd);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int head_bwd_launch(int P, const float *G, int ldg, int inv, int feat, const float *lin0, float *dm, hipStream_t st) {
+    k_head_bwd<<<P, 256, 0, st>>>(G, ldg, inv, feat, lin0, dm);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int lin0_grad_launch(int P, const float *G, int ldg, const float *M, int ldm, int feat, float *dW0, float *db0, hipStream_t st) {
+    k_lin0_grad<<<(2 * feat + 255) / 256, 256, 0, st>>>(P, G, ldg, M, ldm, feat, dW0, db0);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int vn_lin_launch(int P, int Cin, int Cout, const float *X, int ldx, const float *Wf, const float *Wd, float *Pm, float *Dm, hipStream_t st) {
+    k_vn_lin<<<(P * Cout + 255) / 256, 256, 0, st>>>(P, Cin, Cout, X, ldx, Wf, Wd, Pm, Dm);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int vn_stat_launch(int P, int Cout, const float *Pm, double *partial, hipStream_t st) {
+    k_vn_stat<<<Cout, 256, 0, st>>>(P, Cout, Pm, partial);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+int vn_apply_launch(int P, int Cout, const float *Pm, const float *Dm, const float *rec, float *Y, hipStream_t st) {
+    k_vn_apply<<<(P * Cout + 255) / 256, 256, 0, st>>>(P, Cout, Pm, Dm, rec, Y);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
 }  // namespace da
 
@@ -693,11 +803,8 @@ int da_pcd_train_forward(const da_pcd_train_weights *w, int n_parts, int n_point
     const int nblk = (int)((pts + 255) / 256);
     const double n_edge = (double)pts * KNN;
     auto fin = [&](int l, int C, int nb, double count, float *ss, int ss_ld) -> int {
-        k_bn_fin_fwd<<<C, 256, 0, st>>>(W.partial, nb, C, count, w->gamma[l], w->beta[l], w->momentum[l], w->eps[l],
-                                        w->running_mean[l], w->running_var[l], S.rec + (size_t)l * REC * CMAX,
-                                        run_out + (size_t)l * 2 * CMAX, ss, ss_ld);
-        DA_LAUNCH_CHECK();
-        return 0;
+        return bn_fin_fwd_launch(W.partial, nb, C, count, w->gamma[l], w->beta[l], w->momentum[l], w->eps[l], w->running_mean[l],
+                                 w->running_var[l], S.rec + (size_t)l * REC * CMAX, run_out + (size_t)l * 2 * CMAX, ss, ss_ld, st);
     };
     int rc;
     for (int s = 0; s < 3; ++s) {
@@ -710,21 +817,17 @@ int da_pcd_train_forward(const da_pcd_train_weights *w, int n_parts, int n_point
         EdgeArgs a{};
         a.T = W.T; a.idx = S.idx[s]; a.N = N; a.npts = pts; a.partial = W.partial;
         a.recA = S.rec + (size_t)la * REC * CMAX;
-        if (hb) k_pt_edge<M_STAT_A, true><<<nblk, 256, 0, st>>>(a);
-        else k_pt_edge<M_STAT_A, false><<<nblk, 256, 0, st>>>(a);
-        DA_LAUNCH_CHECK();
+        if ((rc = edge_launch(M_STAT_A, hb, a, st))) return rc;
         if ((rc = fin(la, VC, nblk, n_edge, w->bn_a[s], VC))) return rc;
         if (hb) {
             a.wb = w->conv_b[s];
-            k_pt_edge<M_STAT_B, true><<<nblk, 256, 0, st>>>(a);
-            DA_LAUNCH_CHECK();
+            if ((rc = edge_launch(M_STAT_B, true, a, st))) return rc;
             if ((rc = fin(lb, VC, nblk, n_edge, w->conv_b[s] + 2 * VC * (VC + 1), VC))) return rc;
         }
         if ((rc = pcd_edge_launch(W.T, S.idx[s], w->bn_a[s], hb ? w->conv_b[s] : nullptr, N, P, S.X[s], s < 2 ? W.xn[s] : nullptr, st))) return rc;
     }
     // conv6 (BatchNorm1d over the P * N points), mean over points
-    k_c6<C6_STAT><<<nblk, 256, 0, st>>>(S.X[0], S.X[1], S.X[2], w->conv6, feat, N, pts, nullptr, nullptr, W.partial, nullptr, 0, nullptr);
-    DA_LAUNCH_CHECK();
+    if ((rc = c6_launch(C6_STAT, S.X[0], S.X[1], S.X[2], w->conv6, feat, N, pts, nullptr, nullptr, W.partial, nullptr, 0, nullptr, st))) return rc;
     if ((rc = fin(5, feat, nblk, (double)pts, w->conv6 + (size_t)feat * V3 + V3, feat))) return rc;
     if ((rc = pcd_conv6_final_launch(S.X[0], S.X[1], S.X[2], w->conv6, feat, N, P, W.c6part, w->linear0, 0, S.M, 6 * feat, st))) return rc;
     if ((rc = pcd_conv6_final_launch(S.X[0], S.X[1], S.X[2], w->conv6, feat, N, P, W.c6part, w->linear0, inv, out, ld_out, st))) return rc;
@@ -733,16 +836,10 @@ int da_pcd_train_forward(const da_pcd_train_weights *w, int n_parts, int n_point
     for (int v = 0; v < 2; ++v) {
         const float *X = v == 0 ? S.M : W.vY;
         const int ldx = v == 0 ? 6 * feat : feat * 3;
-        const int nt = (P * cout[v] + 255) / 256;
-        k_vn_lin<<<nt, 256, 0, st>>>(P, cin[v], cout[v], X, ldx, w->inv_wf[v], w->inv_wd[v], W.vP, W.vD);
-        DA_LAUNCH_CHECK();
-        k_vn_stat<<<cout[v], 256, 0, st>>>(P, cout[v], W.vP, W.partial);
-        DA_LAUNCH_CHECK();
+        if ((rc = vn_lin_launch(P, cin[v], cout[v], X, ldx, w->inv_wf[v], w->inv_wd[v], W.vP, W.vD, st))) return rc;
+        if ((rc = vn_stat_launch(P, cout[v], W.vP, W.partial, st))) return rc;
         if ((rc = fin(6 + v, cout[v], 1, (double)P, nullptr, 0))) return rc;
-        if (v == 0) {
-            k_vn_apply<<<nt, 256, 0, st>>>(P, cout[v], W.vP, W.vD, S.rec + (size_t)6 * REC * CMAX, W.vY);
-            DA_LAUNCH_CHECK();
-        }
+        if (v == 0 && (rc = vn_apply_launch(P, cout[v], W.vP, W.vD, S.rec + (size_t)6 * REC * CMAX, W.vY, st))) return rc;
     }
     return 0;
 }
@@ -768,12 +865,8 @@ int da_pcd_train_backward(const da_pcd_train_weights *w, int n_parts, int n_poin
     float *rec = S.rec;
     int rc;
     // output -> gradient of the pooled map
-    k_head_bwd<<<P, 256, 0, st>>>(grad_out, ld_g, inv, feat, w->linear0, W.dm);
-    DA_LAUNCH_CHECK();
-    if (inv) {
-        k_lin0_grad<<<(2 * feat + 255) / 256, 256, 0, st>>>(P, grad_out, ld_g, S.M, 6 * feat, feat, g->linear0_w, g->linear0_b);
-        DA_LAUNCH_CHECK();
-    }
+    if ((rc = head_bwd_launch(P, grad_out, ld_g, inv, feat, w->linear0, W.dm, st))) return rc;
+    if (inv && (rc = lin0_grad_launch(P, grad_out, ld_g, S.M, 6 * feat, feat, g->linear0_w, g->linear0_b, st))) return rc;
     // the chunks of a pass, each with its blocks' slots in W.partial (global block index: fixed summation order)
     auto chunks = [&](auto &&body) -> int {
         size_t boff = 0;
@@ -788,28 +881,23 @@ int da_pcd_train_backward(const da_pcd_train_weights *w, int n_parts, int n_poin
     };
     const int nbt = (int)nblk_total(P, N, chunk);
     auto fin_bwd = [&](int l, int C, double count) -> int {
-        k_bn_fin_bwd<<<C, 256, 0, st>>>(W.partial, nbt, C, count, rec + (size_t)l * REC * CMAX, g->gamma[l], g->beta[l]);
-        DA_LAUNCH_CHECK();
-        return 0;
+        return bn_fin_bwd_launch(W.partial, nbt, C, count, rec + (size_t)l * REC * CMAX, g->gamma[l], g->beta[l], st);
     };
     // conv6
     const float *rec6 = rec + (size_t)5 * REC * CMAX;
-    if ((rc = chunks([&](long long off, long long cp, int nb, size_t boff, int) -> int {
-             k_c6<C6_BWD1><<<nb, 256, 0, st>>>(S.X[0] + off * VROW, S.X[1] + off * VROW, S.X[2] + off * VROW, w->conv6, feat, N, cp,
-                                                rec6, W.dm + (off / N) * feat * 3, W.partial + boff * 2 * feat, nullptr, 0, nullptr);
-             DA_LAUNCH_CHECK();
-             return 0;
+    if ((rc = chunks([&](long long off, long long cp, int, size_t boff, int) -> int {
+             return c6_launch(C6_BWD1, S.X[0] + off * VROW, S.X[1] + off * VROW, S.X[2] + off * VROW, w->conv6, feat, N, cp, rec6,
+                              W.dm + (off / N) * feat * 3, W.partial + boff * 2 * feat, nullptr, 0, nullptr, st);
          }))) return rc;
     if ((rc = fin_bwd(5, feat, (double)pts))) return rc;
-    if ((rc = chunks([&](long long off, long long cp, int nb, size_t, int) -> int {
-             k_c6<C6_BWD2><<<nb, 256, 0, st>>>(S.X[0] + off * VROW, S.X[1] + off * VROW, S.X[2] + off * VROW, w->conv6, feat, N, cp,
-                                                rec6, W.dm + (off / N) * feat * 3, nullptr, W.G6, g6, W.F);
-             DA_LAUNCH_CHECK();
+    if ((rc = chunks([&](long long off, long long cp, int, size_t, int) -> int {
+             int r2 = c6_launch(C6_BWD2, S.X[0] + off * VROW, S.X[1] + off * VROW, S.X[2] + off * VROW, w->conv6, feat, N, cp, rec6,
+                                W.dm + (off / N) * feat * 3, nullptr, W.G6, g6, W.F, st);
+             if (r2) return r2;
              const long long rows = cp * 3;
-             k_c6_dx<<<(unsigned)((rows + 255) / 256), 256, 0, st>>>(W.G6, g6, w->conv6, feat, rows, W.dX[0] + off * 3 * VROW,
-                                                                     W.dX[1] + off * 3 * VROW, W.dX[2] + off * 3 * VROW);
-             DA_LAUNCH_CHECK();
-             int r2 = launch_gemm_tn((int)rows, feat, V3, W.G6, g6, W.F, VROW, g->wf[5], V3, W.gpart, st);
+             if ((r2 = c6_dx_launch(W.G6, g6, w->conv6, feat, rows, W.dX[0] + off * 3 * VROW, W.dX[1] + off * 3 * VROW,
+                                    W.dX[2] + off * 3 * VROW, st))) return r2;
+             r2 = launch_gemm_tn((int)rows, feat, V3, W.G6, g6, W.F, VROW, g->wf[5], V3, W.gpart, st);
              return r2 ? r2 : launch_gemm_tn((int)rows, 1, V3, W.G6 + feat, g6, W.F, VROW, g->wd[5], V3, W.gpart, st);
          }))) return rc;
     // stages 3, 2, 1
@@ -830,55 +918,116 @@ int da_pcd_train_backward(const da_pcd_train_weights *w, int n_parts, int n_poin
             return a;
         };
         // sums of the last layer's BatchNorm backward
-        if ((rc = chunks([&](long long off, long long cp, int nb, size_t boff, int) -> int {
-                 const EdgeArgs a = args(off, cp, boff);
-                 if (hb) k_pt_edge<M_BWD1, true><<<nb, 256, 0, st>>>(a);
-                 else k_pt_edge<M_BWD1, false><<<nb, 256, 0, st>>>(a);
-                 DA_LAUNCH_CHECK();
-                 return 0;
+        if ((rc = chunks([&](long long off, long long cp, int, size_t boff, int) -> int {
+                 return edge_launch(M_BWD1, hb, args(off, cp, boff), st);
              }))) return rc;
         if ((rc = fin_bwd(hb ? lb : la, VC, (double)pts * KNN))) return rc;
         if (hb) {
-            if ((rc = chunks([&](long long off, long long cp, int nb, size_t boff, int) -> int {
-                     const EdgeArgs a = args(off, cp, boff);
-                     k_pt_edge<M_BWD2, true><<<nb, 256, 0, st>>>(a);
-                     DA_LAUNCH_CHECK();
+            if ((rc = chunks([&](long long off, long long cp, int, size_t boff, int) -> int {
+                     int r2 = edge_launch(M_BWD2, true, args(off, cp, boff), st);
+                     if (r2) return r2;
                      const int rows = (int)(cp * KNN * 3);
-                     int r2 = launch_gemm_tn(rows, VC, VC, W.Gb, GB_LD, W.Hb, H_LD, g->wf[lb], VC, W.gpart, st);
+                     r2 = launch_gemm_tn(rows, VC, VC, W.Gb, GB_LD, W.Hb, H_LD, g->wf[lb], VC, W.gpart, st);
                      return r2 ? r2 : launch_gemm_tn(rows, VC, VC, W.Gb + VC, GB_LD, W.Hb, H_LD, g->wd[lb], VC, W.gpart, st);
                  }))) return rc;
             if ((rc = fin_bwd(la, VC, (double)pts * KNN))) return rc;
         }
         DA_CHECK_HIP(hipMemsetAsync(W.dWm, 0, (size_t)4 * VC * C * 4, st));
-        if ((rc = chunks([&](long long off, long long cp, int nb, size_t boff, int B) -> int {
+        if ((rc = chunks([&](long long off, long long cp, int, size_t boff, int B) -> int {
                  const EdgeArgs a = args(off, cp, boff);
-                 if (hb) k_pt_edge<M_BWD3, true><<<nb, 256, 0, st>>>(a);
-                 else k_pt_edge<M_BWD3, false><<<nb, 256, 0, st>>>(a);
-                 DA_LAUNCH_CHECK();
-                 const long long ne = cp * KNN;
-                 const unsigned ge = (unsigned)((ne + 255) / 256);
-                 DA_CHECK_HIP(hipMemsetAsync(W.cnt, 0, (size_t)cp * 4, st));
-                 k_rev_count<<<ge, 256, 0, st>>>(ne, N, a.idx, W.cnt);
-                 DA_LAUNCH_CHECK();
-                 k_rev_scan<<<B, 256, 0, st>>>(N, W.cnt, W.ptr, W.cur);
-                 DA_LAUNCH_CHECK();
-                 k_rev_fill<<<ge, 256, 0, st>>>(ne, N, a.idx, W.cur, W.rev);
-                 DA_LAUNCH_CHECK();
-                 k_rev_sort<<<nb, 256, 0, st>>>(cp, W.ptr, W.cnt, W.rev);
-                 DA_LAUNCH_CHECK();
+                 int r2 = edge_launch(M_BWD3, hb, a, st);
+                 if (r2) return r2;
+                 if ((r2 = rev_adj_launch(B, N, a.idx, W.cnt, W.ptr, W.cur, W.rev, st))) return r2;
                  float *dxp = s == 0 ? g->points : W.dX[s - 1] + off * 3 * VROW;
                  if (s == 0) {
                      if (dxp) dxp += off * 3;
                      else dxp = W.F;                       // point gradient not requested: a dead scratch target
-                     k_gather<1><<<nb, 256, 0, st>>>(cp, W.E, W.ptr, W.cnt, W.rev, w->premap[s], xin + off * 3, 3, dxp, W.dTc, W.Xc);
-                 } else {
-                     k_gather<VC><<<nb, 256, 0, st>>>(cp, W.E, W.ptr, W.cnt, W.rev, w->premap[s], xin + off * VROW, VROW, dxp, W.dTc, W.Xc);
                  }
-                 DA_LAUNCH_CHECK();
+                 if ((r2 = gather_launch(C, cp, W.E, W.ptr, W.cnt, W.rev, w->premap[s], xin + off * ldx, ldx, dxp, W.dTc, W.Xc, st))) return r2;
                  return launch_gemm_tn((int)(cp * 3), 4 * VC, C, W.dTc, DT_LD, W.Xc, XC_LD, W.dWm, C, W.gpart, st);
              }))) return rc;
-        k_premap_wgrad<<<(VC * C + 255) / 256, 256, 0, st>>>(C, W.dWm, g->wf[la], g->wd[la]);
-        DA_LAUNCH_CHECK();
+        if ((rc = premap_wgrad_launch(C, W.dWm, g->wf[la], g->wd[la], st))) return rc;
+    }
+    return 0;
+}
+
+int da_pcd_train_pass(int pass, const da_pcd_pass_args *p, void *stream) {
+    DA_REQUIRE(p, "da_pcd_train_pass: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int P = p->n_parts, N = p->n_points, feat = p->feat;
+    const long long pts = (long long)P * N;
+    auto sized = [&](bool lists) { return P >= 1 && N >= (lists ? KNN : 1) && pts * KNN * 3 <= 0x7fffffffLL; };
+    auto feat_ok = [&]() { return feat >= 1 && feat <= 128; };
+    switch (pass) {
+    case DA_PCD_PASS_PREMAP:
+        DA_REQUIRE(sized(false) && (p->cin == 1 || p->cin == VC) && p->x && p->w && p->T && p->ld_x >= 3 * p->cin, "da_pcd_train_pass: premap arguments");
+        return pcd_premap_launch(p->cin, p->x, p->ld_x, p->w, pts, p->T, st);
+    case DA_PCD_PASS_EDGE_STAT_A: case DA_PCD_PASS_EDGE_STAT_B: case DA_PCD_PASS_EDGE_BWD1: case DA_PCD_PASS_EDGE_BWD2:
+    case DA_PCD_PASS_EDGE_BWD3: {
+        const int mode = pass - DA_PCD_PASS_EDGE_STAT_A;      // M_STAT_A .. M_BWD3, same order
+        const bool hb = p->has_b != 0, bwd = mode >= M_BWD1;
+        DA_REQUIRE(sized(true) && p->T && p->idx, "da_pcd_train_pass: edge pass without T / idx");
+        DA_REQUIRE(mode == M_BWD3 || p->partial, "da_pcd_train_pass: edge pass without partial");
+        DA_REQUIRE(mode == M_STAT_A || p->rec_a, "da_pcd_train_pass: edge pass without rec_a");
+        DA_REQUIRE(!hb || mode == M_STAT_A || p->w, "da_pcd_train_pass: edge pass without the conv_b blob");
+        DA_REQUIRE(!bwd || (p->dX_in && (!hb || p->rec_b)), "da_pcd_train_pass: backward edge pass without dX_in / rec_b");
+        DA_REQUIRE(mode != M_BWD2 || (p->Gb && p->Hb), "da_pcd_train_pass: BWD2 without Gb / Hb");
+        DA_REQUIRE(mode != M_BWD3 || p->E, "da_pcd_train_pass: BWD3 without E");
+        EdgeArgs a{};
+        a.T = p->T; a.idx = p->idx; a.N = N; a.npts = pts; a.recA = p->rec_a; a.recB = p->rec_b; a.wb = hb ? p->w : nullptr;
+        a.dX = p->dX_in; a.partial = p->partial; a.Gb = p->Gb; a.Hb = p->Hb; a.E = p->E;
+        return edge_launch(mode, hb, a, st);
+    }
+    case DA_PCD_PASS_C6_STAT: case DA_PCD_PASS_C6_BWD1: case DA_PCD_PASS_C6_BWD2: {
+        const int mode = pass - DA_PCD_PASS_C6_STAT;
+        DA_REQUIRE(sized(false) && feat_ok() && p->X1 && p->X2 && p->X3 && p->w, "da_pcd_train_pass: conv6 arguments");
+        DA_REQUIRE(mode == C6_BWD2 ? (p->G6 && p->F && p->ld_g >= feat + 1) : p->partial != nullptr, "da_pcd_train_pass: conv6 outputs");
+        DA_REQUIRE(mode == C6_STAT || (p->rec_a && p->dm_in), "da_pcd_train_pass: conv6 backward without rec_a / dm_in");
+        return c6_launch(mode, p->X1, p->X2, p->X3, p->w, feat, N, pts, p->rec_a, p->dm_in, p->partial, p->G6, p->ld_g, p->F, st);
+    }
+    case DA_PCD_PASS_C6_DX:
+        DA_REQUIRE(sized(false) && feat_ok() && p->G6 && p->w && p->dX1 && p->dX2 && p->dX3 && p->ld_g >= feat + 1, "da_pcd_train_pass: c6_dx arguments");
+        return c6_dx_launch(p->G6, p->ld_g, p->w, feat, pts * 3, p->dX1, p->dX2, p->dX3, st);
+    case DA_PCD_PASS_BN_FIN_FWD:
+        DA_REQUIRE(p->partial && p->nblk >= 1 && p->channels >= 1 && p->channels <= CMAX && p->count > 1.0 && p->gamma && p->beta &&
+                       p->running_mean && p->running_var && p->rec_a && p->run_out && (!p->ss || p->ld_m >= p->channels),
+                   "da_pcd_train_pass: bn_fin_fwd arguments");
+        return bn_fin_fwd_launch(p->partial, p->nblk, p->channels, p->count, p->gamma, p->beta, p->momentum, p->eps, p->running_mean,
+                                 p->running_var, p->rec_a, p->run_out, p->ss, p->ld_m, st);
+    case DA_PCD_PASS_BN_FIN_BWD:
+        DA_REQUIRE(p->partial && p->nblk >= 1 && p->channels >= 1 && p->channels <= CMAX && p->count >= 1.0 && p->rec_a && p->dgamma && p->dbeta,
+                   "da_pcd_train_pass: bn_fin_bwd arguments");
+        return bn_fin_bwd_launch(p->partial, p->nblk, p->channels, p->count, p->rec_a, p->dgamma, p->dbeta, st);
+    case DA_PCD_PASS_REV_ADJ:
+        DA_REQUIRE(sized(true) && p->idx && p->cnt && p->ptr && p->cur && p->rev, "da_pcd_train_pass: rev_adj arguments");
+        return rev_adj_launch(P, N, p->idx, p->cnt, p->ptr, p->cur, p->rev, st);
+    case DA_PCD_PASS_GATHER:
+        DA_REQUIRE(sized(true) && (p->cin == 1 || p->cin == VC) && p->E && p->cnt && p->ptr && p->rev && p->w && p->x && p->ld_x >= 3 * p->cin &&
+                       p->dXp && p->dTc && p->Xc, "da_pcd_train_pass: gather arguments");
+        return gather_launch(p->cin, pts, p->E, p->ptr, p->cnt, p->rev, p->w, p->x, p->ld_x, p->dXp, p->dTc, p->Xc, st);
+    case DA_PCD_PASS_PREMAP_WGRAD:
+        DA_REQUIRE((p->cin == 1 || p->cin == VC) && p->dWm && p->dwf && p->dwd, "da_pcd_train_pass: premap_wgrad arguments");
+        return premap_wgrad_launch(p->cin, p->dWm, p->dwf, p->dwd, st);
+    case DA_PCD_PASS_HEAD_BWD:
+        DA_REQUIRE(P >= 1 && feat_ok() && p->grad_out && p->dm && (!p->inv || p->w) && p->ld_g >= (p->inv ? 2 * feat : 6 * feat),
+                   "da_pcd_train_pass: head_bwd arguments");
+        return head_bwd_launch(P, p->grad_out, p->ld_g, p->inv, feat, p->w, p->dm, st);
+    case DA_PCD_PASS_LIN0_GRAD:
+        DA_REQUIRE(P >= 1 && feat_ok() && p->grad_out && p->x && p->dwf && p->dwd && p->ld_g >= 2 * feat && p->ld_x >= 3 * feat,
+                   "da_pcd_train_pass: lin0_grad arguments");
+        return lin0_grad_launch(P, p->grad_out, p->ld_g, p->x, p->ld_x, feat, p->dwf, p->dwd, st);
+    case DA_PCD_PASS_VN_LIN:
+        DA_REQUIRE(P >= 1 && p->vn_cin >= 1 && p->channels >= 1 && p->x && p->w && p->w2 && p->vP && p->vD && p->ld_x >= 3 * p->vn_cin,
+                   "da_pcd_train_pass: vn_lin arguments");
+        return vn_lin_launch(P, p->vn_cin, p->channels, p->x, p->ld_x, p->w, p->w2, p->vP, p->vD, st);
+    case DA_PCD_PASS_VN_STAT:
+        DA_REQUIRE(P >= 1 && p->channels >= 1 && p->vP && p->partial, "da_pcd_train_pass: vn_stat arguments");
+        return vn_stat_launch(P, p->channels, p->vP, p->partial, st);
+    case DA_PCD_PASS_VN_APPLY:
+        DA_REQUIRE(P >= 1 && p->channels >= 1 && p->channels <= CMAX && p->vP && p->vD && p->rec_a && p->vY, "da_pcd_train_pass: vn_apply arguments");
+        return vn_apply_launch(P, p->channels, p->vP, p->vD, p->rec_a, p->vY, st);
+    default:
+        DA_REQUIRE(false, "da_pcd_train_pass: unknown pass %d", pass);
     }
     return 0;
 }

@@ -691,6 +691,88 @@ int da_pcd_train_backward(const da_pcd_train_weights *w, int n_parts, int n_poin
                           const float *grad_out, int ld_g, void *state, const da_pcd_train_grads *g, void *workspace,
                           size_t workspace_bytes, int chunk, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Passes of the 3D encoder's training path: ONE pass of da_pcd_train_forward / da_pcd_train_backward on caller-supplied
+ * device buffers, through the launch code those two run (same kernel instantiations, same grids).  For kernel-level
+ * tests (tests/test_gpu_pcd_train_kernels.py, contracts in tests/golden/pcd_train_kernel_refs.py) and for rewrites of
+ * single passes.  No allocation, no synchronisation, every launch on `stream`.  pts = n_parts * n_points; edge e =
+ * point * 20 + rank; idx [pts][20] int32, cloud-local.  Layouts (all fp32 unless noted):
+ *   T       premap rows [pts][A | Ad | U | Ud], 4 x 64 floats per point, each segment 21 x 3 values (channel-major,
+ *           component-minor) + one zero pad: A = Wf[:, :cin] x, Ad = Wd[:, :cin] x, U = (Wf[:, cin:] - Wf[:, :cin]) x, Ud alike;
+ *           an edge's first-layer input is p = A_j + U_i, d = Ad_j + Ud_i
+ *   rec     stat record of a layer [6][256]: rows mean, rstd, gamma, beta (written by BN_FIN_FWD), mean(dy), mean(dy xhat)
+ *           (written by BN_FIN_BWD) of the BatchNorm of the vector norm
+ *   partial block partials [block][2][C] in fp64: the two per-channel sums of the block's 256 points (C = 21 for the edge
+ *           passes, feat for conv6); a block covers points [256 b, 256 b + 256) of the call
+ *   dX      component-major gradient map [pts][3][64]: row (point, k) holds component k of the 21 channels, column 21 is
+ *           zero where a pass writes the map; dX_in is the gradient of a stage's POOLED output (the mean over 20 edges)
+ *   Gb      [edge * 3 + k][44]: dp_b (21) | dd_b (21) | 2 unwritten;  Hb [edge * 3 + k][24]: layer b's input h (21) | 3 unwritten
+ *   E       [edge][128]: dp_a (63: channel-major, component-minor) | 0 | dd_a (63) | 0   (gradients of p, d of layer a)
+ *   dTc     [point * 3 + k][84]: the gradient of T's four segments, component-major;  Xc [point * 3 + k][24]: x, cin used
+ *   G6      [point * 3 + k][ld_g6], ld_g6 = (feat + 4) & ~3: dp6 (feat) | dd6 (1) | unwritten;  F [point * 3 + k][64]:
+ *           cat(x1, x2, x3) component-major (63) | 0
+ *   wb      conv_b blob of da_pcd_encoder_weights: [21][22] feature map, [21][22] direction map (+ scale / shift slots)
+ *   w6      conv6 blob: [feat][63] feature map, [63] direction map (+ scale / shift slots)
+ * Every pass reads only the fields its line names; the others may be NULL / 0.
+ * ------------------------------------------------------------------------------------- */
+enum {
+    DA_PCD_PASS_PREMAP = 0,      /* x (ld_x, cin), w = premap blob [4][21][cin] -> T                                       */
+    DA_PCD_PASS_EDGE_STAT_A,     /* T, idx -> partial: sums of |p_a|+eps and its square (has_b selects the instantiation)  */
+    DA_PCD_PASS_EDGE_STAT_B,     /* T, idx, rec_a, w = wb -> partial: the same for layer b (has_b must be 1)               */
+    DA_PCD_PASS_EDGE_BWD1,       /* T, idx, rec_a[, rec_b, w = wb], dX_in -> partial: sums of dy, dy xhat of the LAST layer */
+    DA_PCD_PASS_EDGE_BWD2,       /* (has_b) ... rec_b with its backward means -> Gb, Hb, partial: sums of layer a          */
+    DA_PCD_PASS_EDGE_BWD3,       /* ... both records complete -> E                                                         */
+    DA_PCD_PASS_C6_STAT,         /* X1, X2, X3 [pts][64], w = w6, feat -> partial [block][2][feat]                         */
+    DA_PCD_PASS_C6_BWD1,         /* ... rec_a, dm [n_parts][feat][3] (gradient of the mean over points) -> partial         */
+    DA_PCD_PASS_C6_BWD2,         /* ... rec_a complete -> G6 (ld_g), F                                                     */
+    DA_PCD_PASS_C6_DX,           /* G6 (ld_g), w = w6, feat -> dX1, dX2, dX3 (written)                                     */
+    DA_PCD_PASS_BN_FIN_FWD,      /* partial, nblk, channels, count, gamma, beta, momentum, eps, running_mean, running_var
+                                    -> rec_a rows 0..3, run_out [2][256] (mean, unbiased variance blended), ss (may be NULL):
+                                    ss[c] = gamma rstd, ss[ld_m + c] = beta - mean gamma rstd                              */
+    DA_PCD_PASS_BN_FIN_BWD,      /* partial, nblk, channels, count -> rec_a rows 4, 5; dgamma += sum dy xhat, dbeta += sum dy */
+    DA_PCD_PASS_REV_ADJ,         /* idx -> cnt, ptr [pts], rev [pts * 20] (cur [pts]: scratch): for every point the edges
+                                    that END in it, ascending; ptr = start in rev, cnt = how many                          */
+    DA_PCD_PASS_GATHER,          /* E, cnt, ptr, rev, w = premap blob, x (ld_x, cin) -> dTc, Xc (written), dXp (ADDED to):
+                                    cin == 1: [pts][3]; cin == 21: component-major map                                     */
+    DA_PCD_PASS_PREMAP_WGRAD,    /* dWm [4][21][cin] -> dwf, dwd [21][2 cin] (ADDED to)                                    */
+    DA_PCD_PASS_HEAD_BWD,        /* grad_out [n_parts][ld_g], inv, feat, w = linear0 (inv) -> dm [n_parts][feat][3]        */
+    DA_PCD_PASS_LIN0_GRAD,       /* grad_out (ld_g), x = pooled map M (ld_x), feat -> dwf [2 feat][3], dwd [2 feat] (ADDED) */
+    DA_PCD_PASS_VN_LIN,          /* x [n_parts] rows of ld_x = [vn_cin][3], w, w2 = map_to_feat / map_to_dir [channels][vn_cin]
+                                    -> vP, vD [n_parts][channels][3]                                                       */
+    DA_PCD_PASS_VN_STAT,         /* vP -> partial [2][channels] (one block partial)                                        */
+    DA_PCD_PASS_VN_APPLY         /* vP, vD, rec_a -> vY [n_parts][channels][3]                                             */
+};
+typedef struct da_pcd_pass_args {
+    int32_t n_parts, n_points;   /* clouds in the buffers, points per cloud (>= 20 for the passes that read idx)          */
+    int32_t cin;                 /* channels of the stage's input: 1 (the points, stage 1) or 21                          */
+    int32_t feat;                /* conv6 output channels, 2..128                                                         */
+    int32_t has_b, inv;
+    int32_t channels, nblk;      /* finalisers / VnInv: channel count (<= 256), number of block partials                  */
+    int32_t ld_x, ld_g, ld_m;    /* row strides in floats                                                                 */
+    int32_t vn_cin;
+    double count;                /* finalisers: elements per channel                                                      */
+    float momentum, eps;
+    const float *x, *w, *w2;
+    float *T;
+    const int32_t *idx;
+    float *rec_a, *rec_b;
+    const float *dX_in;
+    double *partial;
+    float *Gb, *Hb, *E;
+    const float *X1, *X2, *X3, *dm_in;
+    float *G6, *F, *dX1, *dX2, *dX3;
+    const float *gamma, *beta, *running_mean, *running_var;
+    float *run_out, *ss, *dgamma, *dbeta;
+    int32_t *cnt, *ptr, *cur, *rev;
+    float *dXp, *dTc, *Xc;
+    const float *dWm;
+    float *dwf, *dwd;
+    const float *grad_out;
+    float *dm;
+    float *vP, *vD, *vY;
+} da_pcd_pass_args;
+int da_pcd_train_pass(int pass, const da_pcd_pass_args *args, void *stream);
+
 /* Nearest-neighbour squared distances both ways (chamfer_distance.py:148-149 = pytorch3d knn_points K = 1, used by
  * utils_3d.py:1089-1129 calc_part_acc): a [n_clouds, n, 3], b [n_clouds, m, 3] -> d_ab [n_clouds, n],
  * d_ba [n_clouds, m]; either output may be NULL. */
