@@ -112,6 +112,7 @@ int launch_attn_csr(int prec, int n_nodes, const int32_t *row_ptr, const int32_t
 // da_so3.hip (3D head + SO(3) DDIM)
 int launch_head3d(int prec, int n, const void *hh, const float *wt, const float *bt, const float *wr, const float *br,
                   float *out7, float *pre_head, hipStream_t st);
+int launch_head3d_bwd(int n, const float *pre, const float *d_out, float *d_pre, hipStream_t st);     // [r | t] [n, 6], d[q | t] [n, 7] -> d[r | t]
 int launch_ddim3d(const DeviceSchedule &s, int mean_type, int n, const float *x, const float *mo, const int64_t *t,
                   int64_t t_scalar, int ratio, int prev_all_nonneg, float *x_prev, hipStream_t st);
 

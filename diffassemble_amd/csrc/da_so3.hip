@@ -3,6 +3,7 @@
 // matrix_to_quaternion, L2 normalise) and the SE(3) DDIM update
 // (spatial_diffusion_3d_test_double_diffusion.py:595-685 with so3_scale / log_rmat of
 // utils_3d.py:1018-1061).  A few dozen flops per piece: one thread per piece, fp32.
+// Training side: the pose head's backward (k_head3d_bwd) and the SE(3) noising of p_losses (k_q_sample_se3).
 //
 // matrix_exp of a skew matrix is evaluated in closed form (Rodrigues); torch.matrix_exp uses
 // a scaled Taylor/Pade series -- equal to ~1e-7.  log_rmat's NaN branch (rotation by exactly
@@ -167,6 +168,91 @@ __global__ __launch_bounds__(64) void k_ddim3d(DeviceSchedule s, int mean_type, 
     o[0] = qp[0]; o[1] = qp[1]; o[2] = qp[2]; o[3] = qp[3];
 }
 
+// Backward of the pose head (the tail of k_head3d): pre [n, 6] = [r | t] as the forward saved it, d_out [n, 7] the gradient of
+// [q | t] -> d_pre [n, 6].  The translation passes through.  The rotation is q = normalize(matrix_to_quaternion(exp(skew(r)))):
+// on the forward's branch q = s (cos(th/2), k r) with th = |r|, k = sin(th/2) / th and s = +-1 so that w >= 0
+// (standardize_quaternion); |q| = 1, so F.normalize contributes the tangent projection g' = g - q <q, g> and
+//   d r_j = s (-(k/2) r_j g'_w + k g'_j + m r_j <r, g'_v>),   m = (cos(th/2) / 2 - k) / th^2
+// (k -> 1/2 - th^2/48, m -> -1/24 + th^2/960 below rodrigues' th < 1e-4 switch).  One thread per piece, fp32, no atomics.
+__global__ __launch_bounds__(64) void k_head3d_bwd(int n, const float *__restrict__ pre, const float *__restrict__ d_out,
+                                                   float *__restrict__ d_pre) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float r0 = pre[(size_t)i * 6], r1 = pre[(size_t)i * 6 + 1], r2 = pre[(size_t)i * 6 + 2];
+    const float *g = d_out + (size_t)i * 7;
+    const float th2 = r0 * r0 + r1 * r1 + r2 * r2, th = sqrtf(th2);
+    float c, k, m;
+    if (th < 1e-4f) {
+        c = 1.0f - th2 * 0.125f;
+        k = 0.5f - th2 * (1.0f / 48.0f);
+        m = -1.0f / 24.0f + th2 * (1.0f / 960.0f);
+    } else {
+        c = cosf(0.5f * th);
+        k = sinf(0.5f * th) / th;
+        m = (0.5f * c - k) / th2;
+    }
+    const float s = c < 0.f ? -1.f : 1.f;
+    const float qw = s * c, q1 = s * k * r0, q2 = s * k * r1, q3 = s * k * r2;
+    const float dot = qw * g[0] + q1 * g[1] + q2 * g[2] + q3 * g[3];
+    const float gw = g[0] - qw * dot, g1 = g[1] - q1 * dot, g2 = g[2] - q2 * dot, g3 = g[3] - q3 * dot;
+    const float rg = r0 * g1 + r1 * g2 + r2 * g3;
+    const float a = m * rg - 0.5f * k * gw;                 // coefficient of r_j
+    float *o = d_pre + (size_t)i * 6;
+    o[0] = s * (k * g1 + a * r0);
+    o[1] = s * (k * g2 + a * r1);
+    o[2] = s * (k * g3 + a * r2);
+    o[3] = g[4]; o[4] = g[5]; o[5] = g[6];
+}
+
+// SE(3) noising of p_losses (spatial_diffusion_3d_test_double_diffusion.py:421-441) as one launch, one thread per piece:
+// translation = q_sample; rotation = so3_scale(R0, sqrt_alphas_cumprod[t]) @ noise, noise an IGSO(3) draw by inverse-transform
+// sampling on the piece's CDF row trap[t] (IsotropicGaussianSO3.sample, distributions.py:507-526): idx_1 = #{trap[t] <= u}
+// (the row is non-decreasing: a binary search), idx_0 = max(idx_1 - 1, 0), angle = lerp of the two sample locations
+// pi linspace(0, 1, 1000)[1:]^3 with the clamped weight (u - trap_start) / max(trap_end - trap_start, 1e-6).
+// The reference gathers trap_start / trap_end with an index of shape [P, 1] along dim 0 of its [999, P] table, i.e. from the
+// FIRST piece's column whatever the piece (distributions.py:516-517); the weights here come from row t[0] for the same reason.
+// idx_1 can reach 999 for u = 1 (the reference's gather would raise): clamped to 998.
+constexpr int IGSO3_ROW = 999;
+__device__ __forceinline__ float igso3_loc(int k) {                // pi * linspace(0, 1, 1000)[k + 1]^3 (torch's two-sided linspace)
+    const int j = k + 1;
+    const float step = 1.0f / 999.0f;
+    const float x = j < 500 ? step * (float)j : 1.0f - step * (float)(999 - j);
+    return 3.14159265358979323846f * (x * x * x);
+}
+__global__ __launch_bounds__(64) void k_q_sample_se3(int steps, int n, const float *__restrict__ sac, const float *__restrict__ somac,
+                                                     const float *__restrict__ trap, const float *__restrict__ x_start,
+                                                     const int64_t *__restrict__ t, const float *__restrict__ noise_tr,
+                                                     const float *__restrict__ axes, const float *__restrict__ unif,
+                                                     float *__restrict__ x_noisy) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    auto clampt = [&](int64_t v) { return v < 0 ? (int64_t)0 : (v >= steps ? (int64_t)steps - 1 : v); };
+    const int64_t ti = clampt(t[i]), t0 = clampt(t[0]);
+    const float a = sac[ti], b = somac[ti];
+    const float *xs = x_start + (size_t)i * 7;
+    float *o = x_noisy + (size_t)i * 7;
+    for (int c = 0; c < 3; ++c) o[4 + c] = __fadd_rn(__fmul_rn(a, xs[4 + c]), __fmul_rn(b, noise_tr[(size_t)i * 3 + c]));      // k_q_sample's expression
+    const float *row = trap + (size_t)ti * IGSO3_ROW, *row0 = trap + (size_t)t0 * IGSO3_ROW;
+    const float u = unif[i];
+    int lo = 0, hi = IGSO3_ROW;                                    // first index with row[k] > u
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (row[mid] <= u) lo = mid + 1; else hi = mid;
+    }
+    const int idx1 = lo > IGSO3_ROW - 1 ? IGSO3_ROW - 1 : lo, idx0 = idx1 > 0 ? idx1 - 1 : 0;
+    const float ts = row0[idx0], te = row0[idx1];
+    const float diff = fmaxf(te - ts, 1e-6f);
+    const float wgt = fminf(fmaxf((u - ts) / diff, 0.f), 1.f);
+    const float a0 = igso3_loc(idx0), a1 = igso3_loc(idx1);
+    const float ang = wgt < 0.5f ? a0 + wgt * (a1 - a0) : a1 - (a1 - a0) * (1.0f - wgt);      // torch.lerp
+    const float v0 = axes[(size_t)i * 3], v1 = axes[(size_t)i * 3 + 1], v2 = axes[(size_t)i * 3 + 2];
+    const float inv = ang / sqrtf(v0 * v0 + v1 * v1 + v2 * v2);
+    const M3 noise = rodrigues(v0 * inv, v1 * inv, v2 * inv);      // aa_to_rmat(axis, angle)
+    float q[4];
+    mat_to_quat(matmul(so3_scale(quat_to_mat(xs), a), noise), q);
+    o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3];
+}
+
 int launch_head3d(int prec, int n, const void *hh, const float *wt, const float *bt, const float *wr, const float *br,
                   float *out7, float *pre_head, hipStream_t st) {
     if (n <= 0) return 0;
@@ -187,4 +273,36 @@ int launch_ddim3d(const DeviceSchedule &s, int mean_type, int n, const float *x,
     return 0;
 }
 
+int launch_head3d_bwd(int n, const float *pre, const float *d_out, float *d_pre, hipStream_t st) {
+    if (n <= 0) return 0;
+    k_head3d_bwd<<<(n + 63) / 64, 64, 0, st>>>(n, pre, d_out, d_pre);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace da
+
+using namespace da;
+
+extern "C" {
+
+int da_head3d_backward(int n, const float *pre, const float *d_out, float *d_pre, void *stream) {
+    DA_REQUIRE(n >= 0, "da_head3d_backward: n < 0");
+    DA_REQUIRE(pre && d_out && d_pre, "da_head3d_backward: null argument");
+    return launch_head3d_bwd(n, pre, d_out, d_pre, (hipStream_t)stream);
+}
+
+int da_q_sample_se3(int steps, int n, const float *sqrt_alphas_cumprod, const float *sqrt_one_minus_alphas_cumprod, const float *trap,
+                    const float *x_start, const int64_t *t, const float *noise_tr, const float *axes, const float *unif, float *x_noisy,
+                    void *stream) {
+    DA_REQUIRE(steps > 0 && n >= 0, "da_q_sample_se3: steps must be positive and n >= 0");
+    DA_REQUIRE(sqrt_alphas_cumprod && sqrt_one_minus_alphas_cumprod && trap && x_start && t && noise_tr && axes && unif && x_noisy,
+               "da_q_sample_se3: null argument");
+    if (n == 0) return 0;
+    k_q_sample_se3<<<(n + 63) / 64, 64, 0, (hipStream_t)stream>>>(steps, n, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, trap, x_start, t,
+                                                                  noise_tr, axes, unif, x_noisy);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

@@ -40,6 +40,12 @@ __global__ __launch_bounds__(256) void k_gelu_bwd(size_t n, const float *__restr
         dx[i] = dy[i] * gelu_grad(pre[i]);
 }
 
+// dx = dy * (out > 0 ? 1 : 0.2): LeakyReLU(0.2) backward from the layer's OUTPUT (same sign as its input; 0 takes the slope like torch)
+__global__ __launch_bounds__(256) void k_leaky_bwd(size_t n, const float *__restrict__ out, const float *dy, float *dx) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        dx[i] = out[i] > 0.f ? dy[i] : 0.2f * dy[i];
+}
+
 // dst = bf16(src), 8 elements per thread and pass (n a multiple of 8; both 16-byte aligned)
 __global__ __launch_bounds__(256) void k_cast_h(size_t n8, const float *__restrict__ src, bf16_t *__restrict__ dst) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
@@ -831,7 +837,7 @@ static unsigned grid_for(size_t n) { const size_t b = (n + 255) / 256; return (u
 // each): job j of the table = one matrix, mode 0: dst[c][r] = src[r][c] (fp32 W^T for a dX product), 1: the same rounded to bf16
 // (q16 mode), 2: dst[r][c] = bf16(src[r][c]) (the bf16 forward operand of the q16 mode).  grid = (tiles of the largest job, jobs).
 struct WPrepJob { const float *src; void *dst; int rows, cols, mode, pad; };
-struct WPrepTable { WPrepJob job[5 + 2 * DA_MAX_LAYERS]; int n; };
+struct WPrepTable { WPrepJob job[6 + 2 * DA_MAX_LAYERS]; int n; };
 __global__ __launch_bounds__(256) void k_weight_prep(WPrepTable tab) {
     __shared__ float tile[32][33];
     const WPrepJob jb = tab.job[blockIdx.y];
@@ -879,6 +885,7 @@ struct TrainWs {
     float *partial2, *dY4b;            // side-stream dW products: their own split scratch, and the second projection-gradient buffer (see SideDw)
     bf16_t *x16[DA_MAX_LAYERS];        // q16 mode: bf16 image of every conv's input (the projection's operand in the forward, X of its dW product in the backward)
     float *wt_head1, *wt_head0, *wt_mlp1, *wt_mlp0, *wt_pos1;
+    float *wt_head_r1, *pre6, *dpre6;  // 3D: mlp_r.2's W^T; the heads' [r | t] output and its gradient ([nr, 6])
     size_t total;
 };
 
@@ -886,6 +893,8 @@ struct Dims {
     int nr, n, F, D, hid, H, L, V, c_in, c_out, G;
     int din[DA_MAX_LAYERS], C[DA_MAX_LAYERS], hc[DA_MAX_LAYERS];
     bool gelu_between;
+    bool v3d;                  // DA_VARIANT_3D (efficient_gat_3d.py): LeakyReLU mlp, two pose heads behind one 512-wide hidden product
+    int hh;                    // width of the head's hidden layer: 32 (final_mlp.0), 3D: 512 (mlp_t.0 | mlp_r.0)
     bool gcn;                  // DA_ARCH_GCN (backbones/gcn.py): two GCNConv, aggregation by da_gcn.hip, no attention
     bool dense;                // complete graphs: grouped-GEMM attention (da_train_dense.hip)
     bool hybrid;               // hybrid graphs: masked grouped GEMMs + CSR remainder (da_train_dense.hip)
@@ -900,12 +909,16 @@ struct Dims {
 static int dims_of(const da_weights *w, const da_graph *g, Dims &d, int mma = DA_TRAIN_MMA_FP32) {
     d.bfc = mma == DA_TRAIN_MMA_BF16;
     DA_REQUIRE(w && g, "training: null argument");
-    DA_REQUIRE(w->variant == DA_VARIANT_2D, "training: only the 2D denoiser is implemented");
+    DA_REQUIRE(w->variant == DA_VARIANT_2D || w->variant == DA_VARIANT_3D, "training: unknown variant %d", w->variant);
+    d.v3d = w->variant == DA_VARIANT_3D;
+    d.hh = d.v3d ? 512 : 32;
+    DA_REQUIRE(!d.v3d || w->c_in == 7, "training (3D): c_in must be 7 (quaternion wxyz | translation), not %d", w->c_in);
+    DA_REQUIRE(w->c_in >= 1 && w->c_in <= 8, "training: c_in %d outside 1 .. 8", w->c_in);
     d.gcn = w->arch == DA_ARCH_GCN;
     DA_REQUIRE(!d.gcn || w->n_layers == 2, "training: gcn arch needs n_layers = 2 (backbones/gcn.py:9-14)");
     DA_REQUIRE(w->heads == 8 && w->n_layers >= 2 && w->n_layers <= DA_MAX_LAYERS, "training: bad heads / n_layers");
     d.nr = g->n_real; d.n = g->n_nodes; d.F = w->feat_dim; d.D = w->feat_dim + 64; d.hid = w->hidden; d.H = w->heads;
-    d.L = w->n_layers; d.V = w->arch == DA_ARCH_EXOPHORMER ? w->virt_nodes : 0; d.c_in = w->c_in; d.c_out = w->c_out;
+    d.L = w->n_layers; d.V = w->arch == DA_ARCH_EXOPHORMER ? w->virt_nodes : 0; d.c_in = w->c_in; d.c_out = d.v3d ? 7 : w->c_out;
     d.gelu_between = w->arch == DA_ARCH_TRANSFORMER || d.gcn;
     d.G = g->n_graphs;
     DA_REQUIRE(d.D % d.H == 0 && (d.D / d.H) % 8 == 0, "training: D / heads must be a multiple of 8");
@@ -969,8 +982,8 @@ static TrainWs carve_train(const Dims &d, void *base) {
         const size_t ws = (size_t)4 * d.hc[l] * d.din[l];
         wmax = ws > wmax ? ws : wmax;
     }
-    w.f1pre = take(nr * 32);
-    w.f1 = take(nr * 32);
+    w.f1pre = take(nr * d.hh);
+    w.f1 = take(nr * d.hh);
     w.dz = take(n * d.D);
     w.dh0 = take(n * d.D);
     w.dY4 = take(n * 4 * hcmax);
@@ -978,7 +991,7 @@ static TrainWs carve_train(const Dims &d, void *base) {
     w.dxb = take(n * d.D);
     w.Dd = take(n * d.H);
     w.dm1 = take(nr * d.hid);
-    w.df1 = take(nr * 32);
+    w.df1 = take(nr * d.hh);
     w.dcomb = take(nr * d.D);
     w.wt = take(wmax + 1024);
     w.partial = take(PART_CAP);
@@ -1003,16 +1016,28 @@ static TrainWs carve_train(const Dims &d, void *base) {
     }
     w.partial2 = take(PART_CAP);
     w.dY4b = take(n * 4 * hcmax);
-    w.wt_head1 = take((size_t)d.c_out * 32);
-    w.wt_head0 = take((size_t)32 * d.D);
+    w.wt_head1 = take(d.v3d ? (size_t)3 * 256 : (size_t)d.c_out * 32);
+    w.wt_head0 = take((size_t)d.hh * d.D);
     w.wt_mlp1 = take((size_t)d.D * d.hid);
     w.wt_mlp0 = take((size_t)d.hid * d.D);
     w.wt_pos1 = take((size_t)32 * 16);
+    w.wt_head_r1 = w.pre6 = w.dpre6 = nullptr;
+    if (d.v3d) {
+        w.wt_head_r1 = take((size_t)3 * 256);
+        w.pre6 = take(nr * 6);
+        w.dpre6 = take(nr * 6);
+    }
     w.total = off;
     return w;
 }
 
 static int check_fused(const da_weights *w, const Dims &d, const char *what) {
+    if (d.v3d) {
+        DA_REQUIRE(w->head_w0 && w->head_b0 && w->head_w1 && w->head_b1, "%s: 3D head pointers (mlp_t) missing", what);
+        DA_REQUIRE(w->head_r_w0 && w->head_r_b0 && w->head_r_w1 && w->head_r_b1, "%s: 3D head_r_* pointers (mlp_r) missing", what);
+        DA_REQUIRE(w->head_r_w0 == w->head_w0 + (size_t)256 * d.D && w->head_r_b0 == w->head_b0 + 256,
+                   "%s: the 3D heads need mlp_t.0 | mlp_r.0 contiguous in that order, weights and biases (flat parameter buffer)", what);
+    }
     for (int l = 0; l < d.L && d.gcn; ++l)
         DA_REQUIRE(w->conv_wq[l] && w->conv_bq[l], "%s: gcn conv %d pointers (lin.weight, bias) missing", what, l);
     for (int l = 0; l < d.L && !d.gcn; ++l) {
@@ -1043,8 +1068,13 @@ static int weight_prep(const da_weights *w, const Dims &d, TrainWs &ws, hipStrea
         maxt = tiles > maxt ? tiles : maxt;
     };
     static_assert(sizeof(WPrepTable) <= 2048, "the job table travels as a kernel argument");
-    add(w->head_w1, ws.wt_head1, d.c_out, 32, 0);
-    add(w->head_w0, ws.wt_head0, 32, d.D, 0);
+    if (d.v3d) {
+        add(w->head_w1, ws.wt_head1, 3, 256, 0);
+        add(w->head_r_w1, ws.wt_head_r1, 3, 256, 0);
+    } else {
+        add(w->head_w1, ws.wt_head1, d.c_out, 32, 0);
+    }
+    add(w->head_w0, ws.wt_head0, d.hh, d.D, 0);
     add(w->mlp_w1, ws.wt_mlp1, d.D, d.hid, 0);
     add(w->mlp_w0, ws.wt_mlp0, d.hid, d.D, 0);
     add(w->pos_w1, ws.wt_pos1, 32, 16, 0);
@@ -1065,6 +1095,11 @@ static int gelu_fwd(size_t n, const float *src, float *dst, hipStream_t st, bf16
 }
 static int gelu_bwd(size_t n, const float *pre, const float *dy, float *dx, hipStream_t st) {
     k_gelu_bwd<<<grid_for(n), 256, 0, st>>>(n, pre, dy, dx);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+static int leaky_bwd(size_t n, const float *out, const float *dy, float *dx, hipStream_t st) {
+    k_leaky_bwd<<<grid_for(n), 256, 0, st>>>(n, out, dy, dx);
     DA_LAUNCH_CHECK();
     return 0;
 }
@@ -1119,14 +1154,23 @@ static SideDw *side_dw(hipStream_t caller) {
 
 // Linear backward: dW += dY^T X, db += colsum(dY), and (if dX) dX = dY @ W (+ res); WT = the forward's image of W^T (k_weight_prep:
 // fp32, or bf16 when dy16); gelu_pre (optional, same leading dimension as dX): dX *= gelu'(gelu_pre) -- inside the reduction-split
-// product's second kernel where that route is taken, as a launch of its own otherwise.  sd: the dW / db launches go to the side
+// product's second kernel where that route is taken, as a launch of its own otherwise.  act = DA_ACT_LEAKY02: the activation in front
+// of this Linear was LeakyReLU(0.2) and gelu_pre holds its OUTPUT (= X): dX *= (X > 0 ? 1 : 0.2), always as a launch of its own.  sd: the dW / db launches go to the side
 // stream (after an event that says dY is final) and `done`, if given, is recorded behind them
 static int linear_bwd(int M, int N, int K, const float *dY, int ldy, const float *X, int ldx, const void *WT,
                       float *dW, float *db, float *dX, int lddx, const float *res, TrainWs &ws, hipStream_t st, bool bfc,
                       bool dy16 = false, const float *gelu_pre = nullptr, const bf16_t *X16 = nullptr, SideDw *sd = nullptr,
-                      hipEvent_t done = nullptr) {
+                      hipEvent_t done = nullptr, int act = DA_ACT_GELU) {
     int rc;
-    auto gelu_tail = [&]() -> int { return gelu_pre ? gelu_bwd((size_t)M * K, gelu_pre, dX, dX, st) : 0; };      // (every caller's dX is dense: lddx == K)
+    const float *act_ref = gelu_pre;
+    if (act != DA_ACT_GELU) gelu_pre = nullptr;             // (the split product's second kernel fuses the GELU derivative only)
+    // the activation tail walks dX as a dense [M, K] image: a strided dX (the 3D heads' halves, lddx = 512) must not ask for one
+    DA_REQUIRE(!act_ref || !dX || lddx == K, "linear_bwd: an activation reference needs a dense dX (lddx %d != K %d)", lddx, K);
+    auto gelu_tail = [&]() -> int {
+        if (!act_ref) return 0;
+        return act == DA_ACT_LEAKY02 ? leaky_bwd((size_t)M * K, act_ref, dX, dX, st) : gelu_bwd((size_t)M * K, act_ref, dX, dX, st);
+    };
+    auto split_done = [&](int r) -> int { return (r || gelu_pre == act_ref) ? r : gelu_tail(); };      // the split route fused nothing: apply it now
     hipStream_t sw = st;                                    // stream and split scratch of the dW / db launches
     float *part = ws.partial;
     if (sd) {
@@ -1152,14 +1196,14 @@ static int linear_bwd(int M, int N, int K, const float *dY, int ldy, const float
     if (!dX) return 0;
     if (dy16) {
         rc = launch_gemm_mfma_splitk(M, N, K, dY, ldy, WT, nullptr, res, dX, lddx, ws.partial, PART_CAP, st, true, gelu_pre);
-        if (rc >= 0) return rc;
+        if (rc >= 0) return split_done(rc);
         rc = launch_gemm_mfma_mixed(true, false, M, N, K, dY, ldy, WT, nullptr, res, dX, lddx, st);
         if (rc < 0) { set_error("training (q16): dX product %d x %d x %d not covered", M, N, K); return 1; }
         return rc ? rc : gelu_tail();
     }
     if (bfc) {                                              // skinny dX with a long reduction: split over the reduction (one launch + a fixed-order sum)
         rc = launch_gemm_mfma_splitk(M, N, K, dY, ldy, WT, nullptr, res, dX, lddx, ws.partial, PART_CAP, st, false, gelu_pre);
-        if (rc >= 0) return rc;
+        if (rc >= 0) return split_done(rc);
     }
     if ((rc = linear(bfc ? DA_PREC_F32_BF16MMA : DA_PREC_F32, M, N, K, dY, ldy, (const float *)WT, nullptr, DA_ACT_NONE, res, dX, lddx, st))) return rc;
     return gelu_tail();
@@ -1167,9 +1211,13 @@ static int linear_bwd(int M, int N, int K, const float *dY, int ldy, const float
 
 // forward Linear of the training path: the bf16-operand mode tries the reduction-split launch first (skinny outputs with a
 // long reduction: mlp.0 and the head's first layer leave most CUs idle otherwise)
-// act_out (optional, dense [M, Nout] like out): gelu(out) -- written by the split product's second kernel, or by a launch of its own
+// act_out (optional, dense [M, Nout] like out): gelu(out) -- written by the split product's second kernel, or by a launch of its own.
+// act = DA_ACT_LEAKY02 (the 3D mlp): act_out = LeakyReLU_0.2(A W^T + bias) straight from the product's epilogue; `out` is not written (the
+// backward takes the sign from the output)
 static int linear_fw(const Dims &d, TrainWs &ws, int M, int K, int Nout, const float *A, int lda, const float *W, const float *bias,
-                     float *out, int ldo, hipStream_t st, float *act_out = nullptr) {
+                     float *out, int ldo, hipStream_t st, float *act_out = nullptr, int act = DA_ACT_GELU) {
+    if (act == DA_ACT_LEAKY02)
+        return linear(d.bfc ? DA_PREC_F32_BF16MMA : DA_PREC_F32, M, K, Nout, A, lda, W, bias, DA_ACT_LEAKY02, nullptr, act_out, Nout, st);
     if (d.bfc) {
         const int rc = launch_gemm_mfma_splitk(M, K, Nout, A, lda, W, bias, nullptr, out, ldo, ws.partial, PART_CAP, st, false, nullptr, act_out);
         if (rc >= 0) return rc;
@@ -1230,13 +1278,23 @@ int da_train_forward_ex(const da_weights *w, const da_graph *g, const float *x, 
     if ((rc = launch_set_feats(P, nr, d.F, D, feats, ws.comb_in, st))) return rc;
     if ((rc = launch_embed_pos_time(P, nr, d.c_in, d.F, D, x, t, 0, w->steps, w->time_emb, w->pos_w0, w->pos_b0, w->pos_w1,
                                     w->pos_b1, ws.comb_in, st))) return rc;
-    if ((rc = linear_fw(d, ws, nr, D, d.hid, ws.comb_in, D, w->mlp_w0, w->mlp_b0, ws.m1pre, d.hid, st, ws.m1))) return rc;
-    if ((rc = linear(PL, nr, d.hid, D, ws.m1, d.hid, w->mlp_w1, w->mlp_b1, DA_ACT_NONE, nullptr, ws.h0, D, st))) return rc;
+    // mlp: Linear GELU Linear (efficient_gat.py:135); 3D: Linear LeakyReLU(0.2) Linear LeakyReLU(0.2) (efficient_gat_3d.py:136-141)
+    const int mlp_act = d.v3d ? DA_ACT_LEAKY02 : DA_ACT_GELU;
+    if ((rc = linear_fw(d, ws, nr, D, d.hid, ws.comb_in, D, w->mlp_w0, w->mlp_b0, ws.m1pre, d.hid, st, ws.m1, mlp_act))) return rc;
+    if ((rc = linear(PL, nr, d.hid, D, ws.m1, d.hid, w->mlp_w1, w->mlp_b1, d.v3d ? DA_ACT_LEAKY02 : DA_ACT_NONE, nullptr, ws.h0, D, st))) return rc;
     if (d.V > 0) {
         DA_REQUIRE(w->virt_emb, "exophormer: virt_emb missing");
         if ((rc = launch_set_virtual_rows(P, n - nr, d.V, D, w->virt_emb, ws.h0 + (size_t)nr * D, st))) return rc;
     }
     if (sd) { DA_CHECK_HIP(hipStreamWaitEvent(st, ev_images, 0)); side_guard.armed = false; }      // the weight images are there (nothing else runs on the side stream in a forward)
+    // head: final_mlp (efficient_gat.py:145); 3D: mlp_t | mlp_r as one 512-wide hidden product, then the pose head, which leaves its
+    // [r | t] pre-image in pre6 for the backward (efficient_gat_3d.py:207-219)
+    auto head_fw = [&](const float *zin) -> int {
+        int r;
+        if ((r = linear_fw(d, ws, nr, D, d.hh, zin, D, w->head_w0, w->head_b0, ws.f1pre, d.hh, st, ws.f1))) return r;
+        if (d.v3d) return launch_head3d(P, nr, ws.f1, w->head_w1, w->head_b1, w->head_r_w1, w->head_r_b1, out, ws.pre6, st);
+        return launch_head2d(P, nr, d.c_out, ws.f1, w->head_w1, w->head_b1, out, st);
+    };
     if (d.gcn) {
         // gcn.py:16-22 with the inference path's reassociation: P0 = h0 W0^T, pre0 = A_hat P0 + b0, a0 = gelu(pre0),
         // Y = A_hat a0, pre1 = Y W1^T + b1, z = gelu(pre1) + h0.  Saved for the backward: qkvs[0] = P0 (unused), o[0] = pre0,
@@ -1249,8 +1307,7 @@ int da_train_forward_ex(const da_weights *w, const da_graph *g, const float *x, 
         if ((rc = launch_gcn_aggregate(P, g, d.hc[0], dinv, ws.hact[0], nullptr, DA_ACT_NONE, ws.qkvs[1], st))) return rc;
         if ((rc = linear(PL, n, d.hc[0], D, ws.qkvs[1], d.hc[0], w->conv_wq[1], w->conv_bq[1], DA_ACT_NONE, nullptr, ws.o[1], D, st))) return rc;
         if ((rc = launch_gcn_gelu_res((size_t)n * D, ws.o[1], ws.h0, ws.hact[1], st))) return rc;
-        if ((rc = linear_fw(d, ws, nr, D, 32, ws.hact[1], D, w->head_w0, w->head_b0, ws.f1pre, 32, st, ws.f1))) return rc;
-        return launch_head2d(P, nr, d.c_out, ws.f1, w->head_w1, w->head_b1, out, st);
+        return head_fw(ws.hact[1]);
     }
     const float *xin = ws.h0;
     int ldx = D;
@@ -1303,8 +1360,7 @@ int da_train_forward_ex(const da_weights *w, const da_graph *g, const float *x, 
         ldx = d.hc[l];
     }
     const float *z = ws.o[d.L - 1];                           // conv output + combined (efficient_gat.py:144)
-    if ((rc = linear_fw(d, ws, nr, D, 32, z, D, w->head_w0, w->head_b0, ws.f1pre, 32, st, ws.f1))) return rc;
-    return launch_head2d(P, nr, d.c_out, ws.f1, w->head_w1, w->head_b1, out, st);
+    return head_fw(z);
 }
 
 int da_train_backward(const da_weights *w, const da_weights *grads, const da_graph *g, const float *x,
@@ -1351,11 +1407,21 @@ int da_train_backward_stage(const da_weights *w, const da_weights *grads, const 
     if (dw_x16 < 0) dw_x16 = DA_XENV("DA_TRAIN_DW_X16", 0) ? 1 : 0;
     if (do_early) {
     // ---- head: final_mlp.2, GELU, final_mlp.0 (efficient_gat.py:145)
+    if (d.v3d) {
+        // 3D (efficient_gat_3d.py:207-219): d[q | t] -> d[r | t] through the pose head, then mlp_r.2 / mlp_t.2 (K = 256 each, the two
+        // halves of the 512-wide hidden layer), one GELU backward over both halves
+        if ((rc = launch_head3d_bwd(nr, ws.pre6, d_out, ws.dpre6, st))) return rc;
+        if ((rc = linear_bwd(nr, 3, 256, ws.dpre6, 6, ws.f1 + 256, 512, ws.wt_head_r1, G(grads->head_r_w1), G(grads->head_r_b1),
+                             ws.df1 + 256, 512, nullptr, ws, st, d.bfc, false, nullptr, nullptr, sd))) return rc;
+        if ((rc = linear_bwd(nr, 3, 256, ws.dpre6 + 3, 6, ws.f1, 512, ws.wt_head1, G(grads->head_w1), G(grads->head_b1),
+                             ws.df1, 512, nullptr, ws, st, d.bfc, false, nullptr, nullptr, sd))) return rc;
+        if ((rc = gelu_bwd((size_t)nr * 512, ws.f1pre, ws.df1, ws.df1, st))) return rc;
+    } else
     if ((rc = linear_bwd(nr, d.c_out, 32, d_out, d.c_out, ws.f1, 32, ws.wt_head1, G(grads->head_w1), G(grads->head_b1),
                          ws.df1, 32, nullptr, ws, st, d.bfc, false, ws.f1pre, nullptr, sd))) return rc;
     const float *z = d.gcn ? ws.hact[L - 1] : ws.o[L - 1];
     if (n > nr) DA_CHECK_HIP(hipMemsetAsync(ws.dz + (size_t)nr * D, 0, (size_t)(n - nr) * D * 4, st));
-    if ((rc = linear_bwd(nr, 32, D, ws.df1, 32, z, D, ws.wt_head0, G(grads->head_w0), G(grads->head_b0), ws.dz, D, nullptr,
+    if ((rc = linear_bwd(nr, d.hh, D, ws.df1, d.hh, z, D, ws.wt_head0, G(grads->head_w0), G(grads->head_b0), ws.dz, D, nullptr,
                          ws, st, d.bfc, false, nullptr, nullptr, sd))) return rc;
     // residual: z = conv_out + h0  ->  both get dz.  Without virtual rows dh0 = dz is not materialised: layer 0's dX product
     // takes dz as its residual operand and writes dh0 (dz is read-only from here on)
@@ -1416,9 +1482,10 @@ int da_train_backward_stage(const da_weights *w, const da_weights *grads, const 
         k_virt_grad<<<(d.V * D + 255) / 256, 256, 0, st>>>(n - nr, d.V, D, ws.dh0 + (size_t)nr * D, G(grads->virt_emb));
         DA_LAUNCH_CHECK();
     }
-    // ---- mlp.2, GELU, mlp.0 (efficient_gat.py:135)
+    // ---- mlp.2, GELU, mlp.0 (efficient_gat.py:135); 3D: a LeakyReLU behind mlp.2 as well (efficient_gat_3d.py:136-141)
+    if (d.v3d && (rc = leaky_bwd((size_t)nr * D, ws.h0, ws.dh0, ws.dh0, st))) return rc;
     if ((rc = linear_bwd(nr, D, d.hid, ws.dh0, D, ws.m1, d.hid, ws.wt_mlp1, G(grads->mlp_w1), G(grads->mlp_b1), ws.dm1, d.hid,
-                         nullptr, ws, st, d.bfc, false, ws.m1pre, nullptr, sd))) return rc;
+                         nullptr, ws, st, d.bfc, false, d.v3d ? ws.m1 : ws.m1pre, nullptr, sd, nullptr, d.v3d ? DA_ACT_LEAKY02 : DA_ACT_GELU))) return rc;
     if ((rc = linear_bwd(nr, d.hid, D, ws.dm1, d.hid, ws.comb_in, D, ws.wt_mlp0, G(grads->mlp_w0), G(grads->mlp_b0), ws.dcomb, D,
                          nullptr, ws, st, d.bfc, false, nullptr, nullptr, sd))) return rc;
     // ---- concat pieces: [feats | pos | time]

@@ -34,6 +34,55 @@ class Schedule:
             setattr(self.c, k, self.t[k].data_ptr())
 
 
+    def igso3_trap(self):
+        """[steps, 999] fp32 on the schedule's device: the IGSO(3) CDF rows of ``da_q_sample_se3``, built on the host the first
+        time and uploaded once (a constant of the schedule)."""
+        if getattr(self, "_trap", None) is None:
+            self._trap = igso3_trap_table(self.t["sqrt_one_minus_alphas_cumprod"].cpu()).to(self.t["betas"].device).contiguous()
+        return self._trap
+
+
+IGSO3_SAMPLES = 1000      # angle samples of IsotropicGaussianSO3 (distributions.py:491); a CDF row has one entry less
+
+
+def _igso3_density(eps, t):
+    """The IGSO(3) angle density of the reference (``IsotropicGaussianSO3._eps_ft``, distributions.py:532-551) for widths
+    ``eps`` [P] at angles ``t`` [S, 1]: fp64 in the reference's expression order, inf / NaN -> 0, the t -> 0 limit where
+    t == 0, then rounded to fp32."""
+    from math import pi, sqrt
+    var_d = eps.double() ** 2
+    t_d = t.double()
+    vals = sqrt(pi) * var_d ** (-3 / 2) * torch.exp(var_d / 4) * torch.exp(-((t_d / 2) ** 2) / var_d) \
+        * (t_d - torch.exp((-pi ** 2) / var_d)
+           * ((t_d - 2 * pi) * torch.exp(pi * t_d / var_d) + (t_d + 2 * pi) * torch.exp(-pi * t_d / var_d))
+           ) / (2 * torch.sin(t_d / 2))
+    vals[vals.isinf()] = 0.0
+    vals[vals.isnan()] = 0.0
+    t_big, _ = torch.broadcast_tensors(t_d, var_d)
+    lim = sqrt(pi) * (var_d * torch.exp(2 * pi ** 2 / var_d) - 2 * var_d * torch.exp(pi ** 2 / var_d)
+                      + 4 * pi ** 2 * var_d * torch.exp(pi ** 2 / var_d)) * torch.exp(var_d / 4 - (2 * pi ** 2) / var_d) / var_d ** (5 / 2)
+    vals[t_big == 0] = lim.expand_as(vals)[t_big == 0]
+    return vals.float()
+
+
+def igso3_trap_table(sqrt_one_minus_alphas_cumprod):
+    """The normalised trapezoid CDF of the IGSO(3) angle density for EVERY timestep: [steps, 999] fp32 on the CPU, row ``t`` =
+    the column ``IsotropicGaussianSO3(eps).trap[:, p]`` the reference rebuilds on every ``p_losses`` call for a piece ``p`` with
+    ``eps[p] = sqrt_one_minus_alphas_cumprod[t]`` (distributions.py:488-505), in its own expression order -- density in fp64,
+    ``.float()``, trapezoid ``cumsum`` in fp32, division by the last entry -- so the rows carry the same bits.  It depends on
+    the schedule alone: built once on the host, no kernel (``Schedule.igso3_trap`` caches the device copy)."""
+    from math import pi
+    eps = sqrt_one_minus_alphas_cumprod.detach().to("cpu", torch.float32).flatten()
+    locs = (pi * torch.linspace(0, 1.0, IGSO3_SAMPLES) ** 3.0).to(eps).unsqueeze(-1)        # [1000, 1]
+    with torch.no_grad():
+        vals = _igso3_density(eps, locs) * ((1 - locs.cos()) / pi)                          # [1000, steps]
+        vals[(locs == 0).expand_as(vals)] = 0.0
+        sums = vals[:-1] + vals[1:]
+        trap = (torch.diff(locs, dim=0) * sums / 2).cumsum(dim=0)
+        trap = trap / trap[-1, None]
+    return trap.t().contiguous()
+
+
 class DenoiserEngine:
     """Packs an ``Eff_GAT`` / ``Eff_GAT_3d`` state dict (reference key layout, see
     the key list in DESIGN.md section 1) into the HIP library and runs forward / sampling on it."""

@@ -113,8 +113,6 @@ class DenoiserBase(nn.Module):
         of one flat fp32 buffer the first time (and again if their storage was replaced)."""
         te = getattr(self, "_train_engine", None)
         if te is None or not te.still_bound():
-            if self.variant != "2d":
-                raise NotImplementedError("training through the HIP backward covers the 2D denoiser only")
             te = TrainEngine(self, device if device is not None else next(self.parameters()).device)
             self._train_engine = te
         return te

@@ -60,6 +60,8 @@ class Eff_GAT_3d(DenoiserBase):
 
     def forward_with_feats(self, xy_pos: Tensor, time: Tensor, edge_index: Tensor, pcd_feats: Tensor, batch):
         """efficient_gat_3d.py:173-220 -> (hstack(unit quaternion wxyz, translation) [P, 7], attentions)."""
+        if self._wants_grad():       # training: da_train_forward now, da_train_backward under autograd (no attention weights)
+            return self._run_train(xy_pos, time, edge_index, pcd_feats, batch)
         return self._run(xy_pos, time, edge_index, pcd_feats, batch, self.return_attentions)
 
     def pcd_features(self, pcd):
@@ -72,9 +74,17 @@ class Eff_GAT_3d(DenoiserBase):
             with torch.no_grad():
                 return self.pcd_backbone(pcd)
         if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.pcd_backbone.parameters()):
-            # a trainable backbone only makes sense with the 3D model's own training (p_losses, the 3D denoiser backward),
-            # which is not built: the encoder trains on its own through VN_DGCNN (differentiable in train()), or frozen here
+            # a trainable backbone is reached through the 3D model's own training step: GNN_Diffusion.p_losses calls
+            # pcd_features_train, whose output carries the encoder's autograd graph into the denoiser backward's d_feats
             raise NotImplementedError(
-                "training Eff_GAT_3d end to end (the 3D denoiser backward and p_losses) is not built: set freeze_backbone=True, "
-                "run pcd_features under torch.no_grad(), or train the VN_DGCNN backbone directly with your own loss")
+                "pcd_features is the inference-side encoder call: a trainable backbone trains through GNN_Diffusion.p_losses "
+                "(pcd_features_train); set freeze_backbone=True or run pcd_features under torch.no_grad() for features alone")
+        return self.pcd_backbone(pcd)
+
+    def pcd_features_train(self, pcd):
+        """The encoder call of ``p_losses`` (efficient_gat_3d.py:230-236 inside the training step): with a trainable backbone the
+        differentiable ``VN_DGCNN`` (HIP forward and backward in train() mode), so that ``d_feats`` of the denoiser backward
+        flows into the encoder through autograd; with ``freeze_backbone`` the no-grad ``pcd_features``."""
+        if self.pcd_backbone is None or self.freeze_backbone:
+            return self.pcd_features(pcd)
         return self.pcd_backbone(pcd)

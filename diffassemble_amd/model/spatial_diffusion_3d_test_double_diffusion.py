@@ -2,8 +2,12 @@
 ``GNN_Diffusion`` that train_3d.py:19 imports): R^3 Gaussian diffusion on translations, SO(3)
 diffusion on rotations (quaternion wxyz | translation per fragment).  On the hot path:
 ``forward_with_feats`` (:369-382), ``p_sample_ddim`` (:595-663) and ``p_sample_loop``
-(:688-731) run in the HIP library; losses / metrics / mesh export (pytorch3d kNN, chamfer)
-are training-side and out of scope (SURVEY.md 2 #2, #10, #11)."""
+(:688-731) run in the HIP library, and so does the training step of train_3d.py's configuration
+(START_X, ``vn_dgcnn``, ``loss_type="all"``): ``p_losses`` (:410-572) = SE(3) noising in one launch
+(da_q_sample_se3) -> VN-DGCNN encoder -> denoiser forward and backward (da_train_forward / da_train_backward,
+``DenoiserTrainFn``; no torch autograd through the denoiser) -> the assembly losses (da_loss3d_*), then
+``training_step`` (:792-807) and the fused Adafactor of ``configure_optimizers``.  ``use_6dof``,
+``loss_type="split"``, the PointNet encoders, metrics dumps and mesh export stay out of scope."""
 from functools import partial
 from typing import Any
 
@@ -179,8 +183,64 @@ class GNN_Diffusion(LightningModule):
         from .. import losses3d
         return losses3d.assembly_losses(prediction, target, cond, n_batch, valids, n_parts=self.max_num_part, loss_type=loss_type)
 
-    def p_losses(self, *args, **kwargs):
-        raise NotImplementedError("3D training losses (pytorch3d kNN / chamfer) are out of scope: SURVEY.md 2 #2")
+    def q_sample_se3(self, x_start, t, noise=None):
+        """The noising of p_losses (:421-441) as ONE launch (da_q_sample_se3): Gaussian ``q_sample`` on the translation,
+        ``so3_scale(R0, sqrt_alphas_cumprod[t]) @ IGSO(3) draw`` on the rotation, back to a quaternion.  ``noise`` =
+        ``(noise_tr [P, 3], axes [P, 3], unif [P])``; drawn here in the reference's order when None (randn for the
+        translation, randn for the axes, rand for the uniforms), so a seeded run replays the reference's stream."""
+        P = x_start.shape[0]
+        dev = x_start.device
+        if dev.type != "cuda":
+            raise _lib.DaError("q_sample_se3: the tensors must live on the ROCm device (diffassemble_amd has no CPU / eager fallback)")
+        if noise is None:
+            noise = (torch.randn(P, 3, device=dev), torch.randn(P, 3, device=dev), torch.rand(P, device=dev))
+        noise_tr, axes, unif = (n.detach().to(dev, torch.float32).contiguous() for n in noise)
+        if noise_tr.shape != (P, 3) or axes.shape != (P, 3) or unif.shape != (P,) or x_start.shape != (P, 7) or t.shape != (P,):
+            raise ValueError("q_sample_se3: x_start [P, 7], t [P], noise = (noise_tr [P, 3], axes [P, 3], unif [P])")
+        sch = self._schedule()
+        x0 = x_start.detach().to(torch.float32).contiguous()
+        tt = t.detach().to(dev, torch.int64).contiguous()
+        sac = self.sqrt_alphas_cumprod.to(torch.float32).contiguous()
+        out = torch.empty_like(x0)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().da_q_sample_se3(self.steps, P, _lib.ptr(sac), _lib.ptr(sch.t["sqrt_one_minus_alphas_cumprod"]),
+                                                  _lib.ptr(sch.igso3_trap()), _lib.ptr(x0), _lib.ptr(tt), _lib.ptr(noise_tr), _lib.ptr(axes),
+                                                  _lib.ptr(unif), _lib.ptr(out), _lib.stream_ptr(dev)))
+        return out
+
+    def p_losses(self, x_start, t, noise=None, loss_type="l1", cond=None, edge_index=None, batch=None, n_batch=None,
+                 valids=None, pcd_feats=None):
+        """...double_diffusion.py:410-572 -> the ``loss_dict`` of ``loss_type="all"``.  Noising, encoder, denoiser forward +
+        backward and the losses all run in the HIP library; torch autograd only links them (``DenoiserTrainFn``, ``_Loss3d``,
+        the encoder's own Function).  ``noise`` = ``(noise_tr, axes, unif)`` (see ``q_sample_se3``); ``pcd_feats`` (extension,
+        like 2D's ``patch_feats``) bypasses the encoder."""
+        if loss_type != "all":             # the reference raises at :570 ("split" cannot run there: trans_l2_loss without valids)
+            raise NotImplementedError(f"loss_type={loss_type!r}: the 3D model trains with loss_type='all' (train_3d.py)")
+        if self.model_mean_type != ModelMeanType.START_X:
+            raise NotImplementedError(
+                "ModelMeanType.EPSILON: the reference's own 3D p_losses cannot run it -- its target is `noise`, which is None on "
+                "that path (:458-461), and the loss fails with a TypeError; train with ModelMeanType.START_X (train_3d.py)")
+        x_noisy = self.q_sample_se3(x_start, t, noise)
+        if self.steps == 1:
+            x_noisy = torch.zeros_like(x_noisy)
+        if pcd_feats is None:
+            pcd_feats = self.model.pcd_features_train(cond)
+        prediction, _ = self.forward_with_feats(x_noisy, t, edge_index, pcd_feats=pcd_feats, batch=batch, return_attentions=False)
+        return self.pose_losses(prediction, x_start, cond, n_batch, valids, loss_type=loss_type)
+
+    def training_step(self, batch, batch_idx):
+        """...double_diffusion.py:792-807 (the batch_idx == 0 sampling dump omitted, as the 2D step omits its image dumps)."""
+        batch_size = batch.batch.max().item() + 1
+        t = torch.randint(0, self.steps, (batch_size,), device=self.device).long()
+        new_t = torch.gather(t, 0, batch.batch)
+        loss_dict = self.p_losses(batch.x, new_t, loss_type=self.loss_type, cond=batch.pcds, edge_index=batch.edge_index,
+                                  batch=batch.batch, n_batch=len(batch.data_id), valids=batch.valids,
+                                  pcd_feats=getattr(batch, "pcd_feats", None))
+        loss = sum(loss_dict.values())
+        for k, v in loss_dict.items():
+            self.log(k, v)
+        self.log("loss", loss)
+        return loss
 
     # ------------------------------------------------------------------ Lightning hooks (inference callers)
     def initialize_torchmetrics(self, categories):
@@ -254,5 +314,19 @@ class GNN_Diffusion(LightningModule):
         return self.validation_epoch_end(outputs)
 
     def configure_optimizers(self):
+        """Adafactor with transformers' defaults, as the 2D module: on a ROCm device one library call over the training engine's
+        flat buffers (``FusedAdafactor``) when the encoder is frozen or absent, ``HybridAdafactor`` (a second call,
+        ``FusedAdafactorND``, for the encoder's tensors) with a trainable encoder attached; ``fused_optimizer = False`` (class /
+        instance attribute) = transformers' own implementation throughout."""
+        fused = bool(getattr(self, "fused_optimizer", True))
+        if fused and self.device.type == "cuda":
+            enc = getattr(self.model, "pcd_backbone", None)
+            te = self.model.train_engine(self.device)
+            if enc is None or self.model.freeze_backbone or not any(p.requires_grad for p in enc.parameters()):
+                from ..train import FusedAdafactor
+                mine = {id(p) for p in te.params}
+                return FusedAdafactor([p for p in self.parameters() if id(p) in mine], te)
+            from ..train import HybridAdafactor
+            return HybridAdafactor(self.parameters(), te)
         from transformers.optimization import Adafactor
         return Adafactor(self.parameters())

@@ -32,7 +32,7 @@ from .graph_plan import GraphPlan
 
 
 def _param_order(module):
-    """(name, fused-group id or None) in flat-buffer order; names relative to the Eff_GAT module."""
+    """(names in flat-buffer order, number of conv layers); names relative to the Eff_GAT / Eff_GAT_3d module."""
     names = ["time_emb.weight", "pos_mlp.0.weight", "pos_mlp.0.bias", "pos_mlp.2.weight", "pos_mlp.2.bias",
              "mlp.0.weight", "mlp.0.bias", "mlp.2.weight", "mlp.2.bias"]
     n_layers = len(module.gnn_backbone.module_list)
@@ -47,17 +47,25 @@ def _param_order(module):
             continue
         names += [p + f"lin_{k}.weight" for k in ("query", "key", "value", "skip")]
         names += [p + f"lin_{k}.bias" for k in ("query", "key", "value", "skip")]
-    names += ["final_mlp.0.weight", "final_mlp.0.bias", "final_mlp.2.weight", "final_mlp.2.bias"]
+    if getattr(module, "variant", "2d") == "3d":
+        # Eff_GAT_3d's two pose heads: mlp_t.0 | mlp_r.0 adjacent (weights, then biases), so the 512-row first layer of both heads
+        # is ONE gap-free slot -- the trick of the lin_query | key | value | skip groups
+        names += ["mlp_t.0.weight", "mlp_r.0.weight", "mlp_t.0.bias", "mlp_r.0.bias",
+                  "mlp_t.2.weight", "mlp_t.2.bias", "mlp_r.2.weight", "mlp_r.2.bias"]
+    else:
+        names += ["final_mlp.0.weight", "final_mlp.0.bias", "final_mlp.2.weight", "final_mlp.2.bias"]
     return names, n_layers
 
 
 class TrainEngine:
-    """Owns the flat buffers + training workspace of one ``Eff_GAT`` module on one GPU."""
+    """Owns the flat buffers + training workspace of one ``Eff_GAT`` / ``Eff_GAT_3d`` module on one GPU."""
 
     def __init__(self, module, device=None):
         self.lib = _lib.lib()
         params = dict(module.named_parameters())
         names, self.n_layers = _param_order(module)
+        self.variant = getattr(module, "variant", "2d")
+        head0 = "mlp_t.0.weight" if self.variant == "3d" else "final_mlp.0.weight"
         dev = torch.device(device) if device is not None else params[names[0]].device
         if dev.type != "cuda":
             raise _lib.DaError("TrainEngine needs a ROCm device (no CPU path in diffassemble_amd)")
@@ -66,7 +74,8 @@ class TrainEngine:
         self.params = [params[n] for n in names]
         offs, off = [], 0
         for n, p in zip(names, self.params):
-            fused_tail = any(n.endswith(f"lin_{k}.{w}") for k in ("key", "value", "skip") for w in ("weight", "bias"))
+            fused_tail = any(n.endswith(f"lin_{k}.{w}") for k in ("key", "value", "skip") for w in ("weight", "bias")) \
+                or n in ("mlp_r.0.weight", "mlp_r.0.bias")
             if not fused_tail:
                 off = (off + 63) // 64 * 64            # 256-byte aligned slots; fused groups stay gap-free
             offs.append(off)
@@ -76,7 +85,7 @@ class TrainEngine:
         # (final once da_train_backward_stage(EARLY) has run), LATE = [0, early_off) = embeddings, mlp, virtual nodes, conv 0
         # (a one-layer backbone has no conv 1: its early bucket is final_mlp alone, which is what the library's stage cut leaves final)
         conv1 = "gnn_backbone.module_list.1." + ("lin.weight" if module.gnn_backbone.arch == "gcn" else "lin_query.weight")
-        early_name = conv1 if self.n_layers > 1 else "final_mlp.0.weight"
+        early_name = conv1 if self.n_layers > 1 else head0
         self.early_off = offs[names.index(early_name)]
         self.flat = torch.zeros(self.total, dtype=torch.float32, device=dev)
         self.flat_grad = torch.zeros(self.total, dtype=torch.float32, device=dev)
@@ -95,7 +104,7 @@ class TrainEngine:
         self.D = by["mlp.0.weight"].shape[1]
         self.F = self.D - 64
         self.c_in = by["pos_mlp.0.weight"].shape[1]
-        self.c_out = by["final_mlp.2.weight"].shape[0]
+        self.c_out = 7 if self.variant == "3d" else by["final_mlp.2.weight"].shape[0]        # 3D: unit quaternion wxyz | translation
         self.steps = by["time_emb.weight"].shape[0]
         self.hidden = by["mlp.0.weight"].shape[0]
         self.w = self._weights_struct(dict(zip(names, self.views)))
@@ -151,7 +160,7 @@ class TrainEngine:
 
     def _weights_struct(self, by):
         w = _lib.DaWeights()
-        w.variant = _lib.VARIANT_2D
+        w.variant = _lib.VARIANT_3D if self.variant == "3d" else _lib.VARIANT_2D
         w.arch = {"exophormer": _lib.ARCH_EXOPHORMER, "gcn": _lib.ARCH_GCN}.get(self.arch, _lib.ARCH_TRANSFORMER)
         w.steps, w.c_in, w.c_out, w.feat_dim, w.hidden = self.steps, self.c_in, self.c_out, self.F, self.hidden
         w.heads, w.n_layers, w.virt_nodes = 8, self.n_layers, self.virt_nodes
@@ -172,6 +181,11 @@ class TrainEngine:
             w.conv_ws[l], w.conv_bs[l] = P(p + "lin_skip.weight"), P(p + "lin_skip.bias")
         if self.virt_nodes > 0:
             w.virt_emb = P("gnn_backbone.virt_node_embedding.weight")
+        if self.variant == "3d":
+            w.head_w0, w.head_b0, w.head_w1, w.head_b1 = P("mlp_t.0.weight"), P("mlp_t.0.bias"), P("mlp_t.2.weight"), P("mlp_t.2.bias")
+            w.head_r_w0, w.head_r_b0 = P("mlp_r.0.weight"), P("mlp_r.0.bias")
+            w.head_r_w1, w.head_r_b1 = P("mlp_r.2.weight"), P("mlp_r.2.bias")
+            return w
         w.head_w0, w.head_b0 = P("final_mlp.0.weight"), P("final_mlp.0.bias")
         w.head_w1, w.head_b1 = P("final_mlp.2.weight"), P("final_mlp.2.bias")
         return w

@@ -433,8 +433,14 @@ int da_debug_counters(int64_t *out /* host [n] */, int n, int reset);
  *   grads  the same struct filled with the gradient pointers (same layout); the library ADDS
  *          into them (zero them per optimizer step).
  *   d_feats nullable [n_real, F]: gradient w.r.t. the piece features, for a trainable encoder.
- * Only the 2D denoiser (arch transformer / exophormer / gcn) is implemented; any graph type, through
- * the CSR attention kernels (needs g->out_ptr / g->out_dst).  DA_ARCH_GCN: w->conv_wq / conv_bq per layer
+ * Both denoisers (arch transformer / exophormer / gcn) are implemented; any graph type, through
+ * the CSR attention kernels (needs g->out_ptr / g->out_dst).  DA_VARIANT_3D (Eff_GAT_3d, efficient_gat_3d.py:173-220):
+ * c_in = 7, x and out are [n_real, 7] (unit quaternion wxyz | translation); mlp is Linear - LeakyReLU(0.2) - Linear -
+ * LeakyReLU(0.2); the two heads run as one 512-wide hidden product, so head_w0 | head_r_w0 (mlp_t.0 | mlp_r.0, [256, D]
+ * each) must be contiguous in that order and so must head_b0 | head_r_b0 -- in w and in grads; the gradients of the
+ * heads go to head_w0/b0, head_w1/b1 (mlp_t) and head_r_w0/b0, head_r_w1/b1 (mlp_r); d_out [n_real, 7] is pulled back
+ * through normalize(matrix_to_quaternion(exp(skew(r)))) by da_head3d_backward's kernel.  The conv stack does not depend
+ * on the variant.  DA_ARCH_GCN: w->conv_wq / conv_bq per layer
  * (lin.weight, bias) only; complete graphs and banded Exphander plans aggregate in closed form, any other
  * plan over its CSR (by destination forward, by source -- out_ptr / out_dst -- backward).  The forward must precede the
  * backward on the same workspace, with the same weights: besides the activations it leaves the
@@ -476,7 +482,7 @@ int da_train_backward_ex(const da_weights *w, const da_weights *grads, const da_
                          size_t workspace_bytes, int mma_precision, void *stream);
 /* ABI 18: the backward in two halves for a BUCKETED data-parallel exchange (the reference gets this from Lightning's DDP reducer,
  * train_script.py:215-218: gradient buckets all-reduced while the rest of backward still runs).  DA_TRAIN_BWD_EARLY enqueues
- * final_mlp and the convs L-1 .. 1 -- afterwards their gradients are final and may be exchanged on another stream --,
+ * final_mlp (3D: mlp_t / mlp_r) and the convs L-1 .. 1 -- afterwards their gradients are final and may be exchanged on another stream --,
  * DA_TRAIN_BWD_LATE conv 0, the virtual-node embedding, mlp, pos_mlp, time_emb (and d_feats).  EARLY followed by LATE on one
  * stream enqueues exactly the launches of DA_TRAIN_BWD_ALL (= da_train_backward_ex).                                       */
 #define DA_TRAIN_BWD_ALL 0
@@ -496,6 +502,26 @@ int da_train_backward_stage(const da_weights *w, const da_weights *grads, const 
 int da_q_sample(int steps, int n, int c, const float *sqrt_alphas_cumprod, const float *sqrt_one_minus_alphas_cumprod,
                 const float *x_start, const float *noise, const int64_t *t, float *x_noisy, void *stream);
 int da_loss_grad(int kind, size_t n, const float *target, const float *pred, float *loss, float *d_pred, void *stream);
+
+/* The 3D model's training glue (additive to ABI 19):
+ *   da_head3d_backward  the pose head's backward on its own: pre [n, 6] = [r | t] (what the head's second Linear layers
+ *                       produce), d_out [n, 7] the gradient of [q | t], q = normalize(matrix_to_quaternion(exp(skew(r))))
+ *                       -> d_pre [n, 6].  Closed form on the branch the forward takes (w >= 0), series below |r| = 1e-4.
+ *   da_q_sample_se3     p_losses' noising, spatial_diffusion_3d_test_double_diffusion.py:421-441, one launch: x_noisy[:, 4:] =
+ *                       q_sample of the translation with noise_tr; x_noisy[:, :4] = matrix_to_quaternion(so3_scale(R(x_start),
+ *                       sqrt_alphas_cumprod[t]) @ N), N the IGSO(3) draw of IsotropicGaussianSO3(sqrt_one_minus_alphas_cumprod[t])
+ *                       .sample() for the given axes (normalised here) and uniforms.  trap [steps, 999]: the normalised
+ *                       trapezoid CDF of every timestep (diffassemble_amd.engine.igso3_trap_table, built once per schedule on
+ *                       the host).  x_start, x_noisy [n, 7]; t [n] int64; noise_tr, axes [n, 3]; unif [n]; all fp32.
+ *                       NOTE: piece i's rotation depends on t[0] as well as on t[i].  The reference gathers the two CDF values of
+ *                       the lerp weight with an index of shape [P, 1] along dim 0 of its [999, P] table, i.e. from the FIRST
+ *                       piece's column for every piece (distributions.py:516-517); the search itself uses the piece's own row.
+ *                       The kernel does the same (weight from row t[0], indices from row t[i]) to reproduce the reference's
+ *                       x_noisy; a caller that wants per-piece weights calls it once per distinct t[0].                     */
+int da_head3d_backward(int n, const float *pre, const float *d_out, float *d_pre, void *stream);
+int da_q_sample_se3(int steps, int n, const float *sqrt_alphas_cumprod, const float *sqrt_one_minus_alphas_cumprod, const float *trap,
+                    const float *x_start, const int64_t *t, const float *noise_tr, const float *axes, const float *unif,
+                    float *x_noisy, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Fused Adafactor step over the flat parameter / gradient buffers (one call = one optimizer
