@@ -235,6 +235,7 @@ PROTOTYPES = {
     "da_pcd_train_pass": (C.c_int, [C.c_int, C.POINTER(DaPcdPassArgs), _fp]),
     "da_knn": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp]),
     "da_nearest_sq": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
+    "da_metrics3d": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, C.c_float, _fp, _fp, _fp]),
     "da_loss3d_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "da_loss3d_forward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_float, C.c_float, C.c_float, _fp, _fp, _fp,
                                     _fp, C.c_size_t, _fp]),

@@ -255,25 +255,25 @@ class GNN_Diffusion(LightningModule):
 
     @torch.no_grad()
     def _eval_step(self, batch, batch_idx):
-        """validation_step / test_step (:895-960, :1036-1080): one sampling loop for the whole Batch, then per object
-        the four pose metrics against the ground-truth poses in ``batch.x`` (wandb / mesh dumps omitted).  Returns the
-        final poses [P, 7]."""
+        """validation_step / test_step (:895-960, :1036-1080): one sampling loop for the whole Batch, then the four pose
+        metrics of every object against the ground-truth poses in ``batch.x`` (wandb / mesh dumps omitted): one
+        ``metrics3d.batch_metrics`` call (``da_metrics3d``) and one [G, 4] copy to the host per Batch.  Returns
+        the final poses [P, 7]."""
         sampled_pos, _ = self.p_sample_loop(batch.x.shape, batch.pcds, batch.edge_index, batch=batch.batch,
                                             pcd_feats=getattr(batch, "pcd_feats", None))
         final_pos = sampled_pos[-1]
-        G = int(batch.batch.max()) + 1
-        for i in range(G):
-            idx = torch.where(batch.batch == i)[0]
-            gt_pos, pred_pos = batch.x[idx], final_pos[idx]
-            pred_r, pred_t, gt_r, gt_t = pred_pos[:, :4], pred_pos[:, 4:7], gt_pos[:, :4], gt_pos[:, 4:]
-            vals = {"rmse_t": metrics3d.trans_metrics(pred_t, gt_t),
-                    "rmse_r": metrics3d.rot_metrics(pred_r, gt_r, "rmse"),
-                    "gd_r": metrics3d.rot_metrics(pred_r, gt_r, "geodesic")}
-            if getattr(batch, "pcds", None) is not None:
-                vals["part_acc"] = metrics3d.calc_part_acc(batch.pcds[idx], pred_t, gt_t, pred_r, gt_r)
-            if hasattr(self, "metrics"):
+        pcds = getattr(batch, "pcds", None)
+        cats = getattr(batch, "category", None)
+        if cats is not None:                   # the object count is known on the host: ptr without reading the device
+            ptr = torch.searchsorted(batch.batch, torch.arange(len(cats) + 1, device=batch.batch.device)).to(torch.int32)
+            vals = metrics3d.batch_metrics(pcds, final_pos, batch.x, ptr=ptr).cpu()
+        else:
+            vals = metrics3d.batch_metrics(pcds, final_pos, batch.x, batch=batch.batch).cpu()
+        if hasattr(self, "metrics"):
+            names = ("rmse_t", "rmse_r", "gd_r") + (("part_acc",) if pcds is not None else ())
+            for i, row in enumerate(vals.tolist()):
                 cat = batch.category[i]
-                for k, v in vals.items():
+                for k, v in zip(names, row):
                     if f"{k}_{cat}" in self.metrics:
                         self.metrics[f"{k}_{cat}"].update(v)
         # (the step only UPDATES the per-category metrics; they are computed, logged and reset once per epoch in

@@ -804,6 +804,19 @@ int da_pcd_train_pass(int pass, const da_pcd_pass_args *args, void *stream);
  * d_ba [n_clouds, m]; either output may be NULL. */
 int da_nearest_sq(int n_clouds, int n, int m, const float *a, const float *b, float *d_ab, float *d_ba, void *stream);
 
+/* The pose metrics of a whole 3D Batch in two launches (utils_3d.py:362-383 trans_metrics, :415-450 rot_metrics 'rmse' and
+ * 'geodesic', :916-945 geodesic_distance, :1089-1129 calc_part_acc, as called per object at
+ * spatial_diffusion_3d_test_double_diffusion.py:895-960, 1036-1080).  pred / gt: pose rows (quaternion wxyz | translation)
+ * of n_parts parts, row strides ld_pred / ld_gt >= 7; pcds [n_parts, n_points, 3] or NULL; ptr int32 [n_objects + 1]: the
+ * parts of object g are rows ptr[g] .. ptr[g + 1] - 1 (ragged; clamped to 0 .. n_parts).
+ * per_part [n_parts, 4] = (rmse_t, rmse_r in degrees, gd_r, two-sided mean squared Chamfer distance between the fragment
+ * posed with pred and with gt); per_object [n_objects, 4] = the mean over the object's parts of columns 0 .. 2 and
+ * part_acc = #{chamfer < thr} / parts.  With pcds == NULL no search runs and both fourth columns are NaN; an object
+ * without parts gets a NaN row.  The posed clouds never reach memory.  fp32, no allocation, no synchronisation, both
+ * launches on `stream`, no floating-point atomics: bitwise reproducible. */
+int da_metrics3d(int n_parts, int n_points, int n_objects, const float *pred, int ld_pred, const float *gt, int ld_gt,
+                 const float *pcds, const int32_t *ptr, float thr, float *per_part, float *per_object, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * The 3D assembly losses of loss_type="all" (model/utils_3d.py:585-890 as called at
  * spatial_diffusion_3d_test_double_diffusion.py:500-562): trans_l2_loss, shape_cd_loss and rot_cosine_loss per shape,
