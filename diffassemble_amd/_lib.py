@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("DA_LIB_PATH") or os.path.join(os.path.dirname(os.path
 DA_MAX_LAYERS = 8
 ABI_VERSION = 19
 PREC_F32, PREC_BF16 = 0, 1
-VARIANT_2D, VARIANT_3D = 0, 1
+VARIANT_2D, VARIANT_3D, VARIANT_DISCRETE = 0, 1, 2
 ARCH_TRANSFORMER, ARCH_EXOPHORMER, ARCH_GCN = 0, 1, 2
 MEAN_EPSILON, MEAN_START_X = 0, 1
 ACT_NONE, ACT_GELU, ACT_LEAKY02 = 0, 1, 2
@@ -65,6 +65,11 @@ class DaGraph(C.Structure):
 class DaLoopOpts(C.Structure):
     """da_loop_opts: sampler 0 = DDIM / 1 = DDPM, eta, classifier-free guidance switch + weight, per-iteration noise."""
     _fields_ = [("sampler", C.c_int32), ("eta", C.c_float), ("cfg", C.c_int32), ("cfg_w", C.c_float), ("noise", C.c_void_p)]
+
+
+class DaD3pmOpts(C.Structure):
+    """da_d3pm_opts: classifier-free guidance switch + weight, injected uniforms [n_iters, n_real, K] or the device {seed, offset} pair."""
+    _fields_ = [("cfg", C.c_int32), ("cfg_w", C.c_float), ("noise", C.c_void_p), ("seed", C.c_void_p)]
 
 
 class DaSchedule(C.Structure):
@@ -188,6 +193,11 @@ PROTOTYPES = {
                                          C.POINTER(DaGraph), _fp, _fp, _fp, C.c_size_t,
                                          C.POINTER(DaGraph), _fp, _fp, _fp, C.c_size_t, _fp, _fp, C.c_size_t,
                                          C.POINTER(DaLoopOpts), _fp, C.c_size_t, _fp]),
+    "da_denoiser_forward_idx": (C.c_int, [_fp, C.POINTER(DaGraph), _fp, _fp, C.c_int64, _fp, _fp, C.c_int, _fp, C.c_size_t, _fp]),
+    "da_d3pm_step": (C.c_int, [C.POINTER(DaSchedule), C.c_int, C.c_int, _fp, _fp, _fp, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, _fp]),
+    "da_d3pm_noise": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "da_sample_loop_idx": (C.c_int, [_fp, C.POINTER(DaGraph), C.POINTER(DaSchedule), C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t,
+                                     C.c_int, C.POINTER(DaD3pmOpts), _fp]),
     "da_profile_enable": (C.c_int, [_fp, C.c_int]),
     "da_profile_read": (C.c_int, [_fp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "da_linear": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int, _fp, _fp,

@@ -73,6 +73,7 @@ struct LoopKey {
     size_t traj_stride;       // elements between consecutive iterations of `traj` (0 = n_real * c)
     size_t noise_stride;      // the same for opts.noise (two-branch loops read row ranges of one [n_iters, N, c] buffer)
     da_config cfg;            // the switches the graph was recorded under (da_config_set between two calls records a new graph)
+    const void *seed;         // da_sample_loop_idx: the device {seed, offset} pair the recorded kernels read (NULL otherwise)
 };
 
 }  // namespace da
@@ -143,6 +144,7 @@ namespace da {
 
 struct Workspace {
     char *comb_in, *h, *combined, *qkvs, *xa, *xb, *z, *hh;
+    char *hh_unc, *pz_unc, *head_pre_unc;   // discrete variant: the unconditional pass's head rows (guidance: both passes' rows feed ONE tail kernel)
     void *pz;                         // [H, n_real, 32] act dtype: per-head outputs of the folded last attention
     char *head_pre;                   // [n_real, 32] act dtype: residual share of final_mlp.0 (fused_mlp2)
     char *feat_proj;                  // [n_real, hidden] act dtype: mlp.0 over the piece-feature columns (+ bias), once per Batch
@@ -184,6 +186,10 @@ static Workspace carve(const da_denoiser *d, const da_graph *g, void *base) {
     w.xb = take(np * 256 * s);
     w.z = take(np * d->D * s);
     w.hh = take(nrp * d->head_hidden * s);
+    const bool disc = d->variant == DA_VARIANT_DISCRETE;
+    w.hh_unc = take(disc ? nrp * d->head_hidden * s : 0);
+    w.pz_unc = take(disc ? nrp * 32 * (size_t)d->heads * sizeof(float) : 0);
+    w.head_pre_unc = take(disc ? nrp * 32 * s : 0);
     w.dq = w.dk = w.dvt = w.dskip = nullptr;
     w.virt_cnt = nullptr; w.virt_part = nullptr;
     w.dense_off = off;
@@ -283,9 +289,22 @@ static int timed(da_denoiser *d, int cls, hipStream_t st, F &&launch) {
     return rc;
 }
 
+// The discrete variant's inputs (da_d3pm.hip): position indices where the poses were; forward_impl then stops behind final_mlp.0 and
+// leaves its post-GELU rows in `hh` -- the K-wide head belongs to the tail kernel, which the caller launches.
+// With the last-layer fold the rows stay one step earlier: per-head outputs `pz` of the folded attention and the pre-activation addend
+// `pre` (hh = GELU(pre + sum_h pz_h), formed by the tail kernel as k_head_fold forms it); `folded` says which form this pass left.
+struct DiscreteIn {
+    const int32_t *idx;     // [n_real]
+    char *hh;               // [n_real, 32] act dtype
+    char *pz, *pre;         // [H, n_real, 32], [n_real, 32] act dtype
+    int folded;             // out
+    D3pmRows rows() const { D3pmRows r; if (folded) { r.pz = pz; r.pre = pre; } else r.hh = hh; return r; }
+};
+
 static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const int64_t *t, int64_t t_scalar,
                         float *out, float *alpha, int alpha_all, float *pre_head, const Workspace &w,
-                        hipStream_t st, DdimFuse *ddim = nullptr, bool uncond = false, bool h_ready = false) {
+                        hipStream_t st, DdimFuse *ddim = nullptr, bool uncond = false, bool h_ready = false,
+                        DiscreteIn *disc = nullptr) {
     const int prec = d->prec, nr = g->n_real, n = g->n_nodes, D = d->D;
     int rc;
     // (a-3) embedding: pose MLP + learned timestep lookup into the concat buffer, then mlp
@@ -299,6 +318,11 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
         vsc.src = d->virt_qkvs_d; vsc.row_map = g->row_map; vsc.Q = w.dq; vsc.K = w.dk; vsc.Vt = w.dvt; vsc.S = w.dskip;
         virt_scattered = true;
     }
+    if (disc) {
+        disc->folded = 0;
+        if ((rc = timed(d, DA_PROF_EMBED, st, [&] {
+                 return launch_embed_idx_time(prec, nr, d->c_out, d->F, D, disc->idx, t, t_scalar, d->steps, d->time_emb, d->pos_w1, w.comb_in, st); }))) return rc;
+    } else
     if (!h_ready && (rc = timed(d, DA_PROF_EMBED, st, [&] {
              return launch_embed_pos_time(prec, nr, d->c_in, d->F, D, x, t, t_scalar, d->steps, d->time_emb,
                                           d->pos_w0, d->pos_b0, d->pos_w1, d->pos_b1, w.comb_in, st, virt_scattered ? &vsc : nullptr); }))) return rc;
@@ -368,7 +392,7 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
                 DenseLayout L;
                 L.Q = w.dq; L.K = w.dk; L.Vt = w.dvt; L.S = nullptr; L.n_pad = g->n_pad; L.q_prescaled = d->q_prescaled;
                 DenseFold fo;
-                fo.cv = 32; fo.out = w.pz; fo.n_rows = nr;
+                fo.cv = 32; fo.out = disc ? (void *)disc->pz : w.pz; fo.n_rows = nr;
                 // hybrid graphs: adjacency-masked, remainder edges of the real rows folded in the epilogue; the
                 // virtual rows' outputs of the LAST layer are dropped by the model (exophormer_gnn.py:209), so the
                 // CSR-side kernels are not needed here
@@ -378,6 +402,15 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
                                              g->pad_ptr, g->dense == 2, nullptr, DA_ACT_NONE, nullptr, st,
                                              g->hybrid ? &mk : nullptr, &fo); });
                 if (rc > 0) return rc;
+                if (rc == 0 && disc) {
+                    // discrete variant: the addend of final_mlp.0 (mlp.2 share + skip share); the K-wide head is the tail kernel's
+                    if ((rc = timed(d, DA_PROF_HEAD, st, [&] {
+                             return linear(prec, nr, d->hidden, 32, w.h, d->hidden, d->headc_w, d->headc_b, DA_ACT_NONE, nullptr, disc->pre, 32, st); }))) return rc;
+                    if ((rc = timed(d, DA_PROF_HEAD, st, [&] {
+                             return linear(prec, nr, c.din, 32, xin, ldx, d->skipc_w, d->skipc_b, DA_ACT_NONE, disc->pre, disc->pre, 32, st); }))) return rc;
+                    disc->folded = 1;
+                    return 0;
+                }
                 if (rc == 0) {
                     // the whole tail in one kernel where it is covered (bf16, hidden 128, conv input 256) ...
                     {
@@ -522,22 +555,24 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
         ldx = c.hc;
     }
     // (a-7 / a-13) pose head
+    char *const hh = disc ? disc->hh : w.hh;
     if (fused) {
         // final_mlp.0(conv_out + combined) = Wf . conv_out + (Wf W2) . h + (Wf b2 + bf): the second term first
         if ((rc = timed(d, DA_PROF_HEAD, st, [&] {
                  return linear(prec, nr, d->hidden, 32, w.h, d->hidden, d->headc_w, d->headc_b, DA_ACT_NONE, nullptr, w.head_pre, 32, st); }))) return rc;
         rc = timed(d, DA_PROF_HEAD, st, [&] {
-            return launch_gemm_mfma(prec, nr, D, d->head_hidden, w.z, D, d->head_w0, d->head_b0, DA_ACT_GELU, nullptr, w.hh,
+            return launch_gemm_mfma(prec, nr, D, d->head_hidden, w.z, D, d->head_w0, d->head_b0, DA_ACT_GELU, nullptr, hh,
                                     d->head_hidden, nullptr, st, D, w.head_pre); });
         if (rc > 0) return rc;
         DA_REQUIRE(rc == 0, "fused head GEMM: shape not supported");
     } else if ((rc = timed(d, DA_PROF_HEAD, st, [&] {
-             return linear(prec, nr, D, d->head_hidden, w.z, D, d->head_w0, d->head_b0, DA_ACT_GELU, nullptr, w.hh,
+             return linear(prec, nr, D, d->head_hidden, w.z, D, d->head_w0, d->head_b0, DA_ACT_GELU, nullptr, hh,
                            d->head_hidden, st); }))) return rc;
+    if (disc) return 0;
     return timed(d, DA_PROF_HEAD, st, [&] {
         if (d->variant == DA_VARIANT_3D)
-            return launch_head3d(prec, nr, w.hh, d->head_w1, d->head_b1, d->head_r_w1, d->head_r_b1, out, pre_head, st);
-        return launch_head2d(prec, nr, d->c_out, w.hh, d->head_w1, d->head_b1, out, st);
+            return launch_head3d(prec, nr, hh, d->head_w1, d->head_b1, d->head_r_w1, d->head_r_b1, out, pre_head, st);
+        return launch_head2d(prec, nr, d->c_out, hh, d->head_w1, d->head_b1, out, st);
     });
 }
 
@@ -564,6 +599,15 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
     // k_embed_pos_time keeps the pose-MLP weight rows in a fixed register array (da_basic.hip); fail here, not on the first
     // forward or inside a hipGraph capture (the reference uses c_in = 2 / 4 in 2D and 7 in 3D)
     DA_REQUIRE(w->c_in >= 1 && w->c_in <= 8, "da_denoiser_create: c_in = %d outside [1, 8]", w->c_in);
+    DA_REQUIRE(w->variant == DA_VARIANT_2D || w->variant == DA_VARIANT_3D || w->variant == DA_VARIANT_DISCRETE, "bad variant %d", w->variant);
+    const bool discrete = w->variant == DA_VARIANT_DISCRETE;
+    if (discrete) {
+        // Eff_GAT_Discrete (efficient_gat_discrete.py:19-51): an index in, K logits out, always the transformer
+        DA_REQUIRE(w->c_in == 1, "da_denoiser_create(discrete): c_in must be 1 (one position index per piece), got %d", w->c_in);
+        DA_REQUIRE(w->c_out >= 2 && w->c_out <= 1024, "da_denoiser_create(discrete): K = c_out = %d outside [2, 1024]", w->c_out);
+        DA_REQUIRE(w->arch == DA_ARCH_TRANSFORMER, "da_denoiser_create(discrete): arch must be DA_ARCH_TRANSFORMER");
+        DA_REQUIRE(w->pos_w1 && w->head_w1 && w->head_b1, "da_denoiser_create(discrete): pos_w1 (pos_mlp.weight [K, 32]) / head_w1 / head_b1 missing");
+    }
     hipStream_t st = (hipStream_t)stream;
     da_denoiser *d = new da_denoiser();
     d->prec = precision; d->variant = w->variant; d->arch = w->arch; d->steps = w->steps; d->c_in = w->c_in;
@@ -609,8 +653,12 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
         return p;
     };
     d->time_emb = copy_f32(w->time_emb, (size_t)w->steps * 32);
-    d->pos_w0 = copy_f32(w->pos_w0, 16 * (size_t)w->c_in); d->pos_b0 = copy_f32(w->pos_b0, 16);
-    d->pos_w1 = copy_f32(w->pos_w1, 32 * 16); d->pos_b1 = copy_f32(w->pos_b1, 32);
+    if (discrete) {
+        d->pos_w1 = copy_f32(w->pos_w1, (size_t)w->c_out * 32);        // pos_mlp.weight [K, 32]; pos_w0 / pos_b0 / pos_b1 are not read
+    } else {
+        d->pos_w0 = copy_f32(w->pos_w0, 16 * (size_t)w->c_in); d->pos_b0 = copy_f32(w->pos_b0, 16);
+        d->pos_w1 = copy_f32(w->pos_w1, 32 * 16); d->pos_b1 = copy_f32(w->pos_b1, 32);
+    }
     d->mlp_w0 = pack(w->mlp_w0, (size_t)d->hidden * D); d->mlp_b0 = copy_f32(w->mlp_b0, d->hidden);
     d->mlp_w1 = pack(w->mlp_w1, (size_t)D * d->hidden); d->mlp_b1 = copy_f32(w->mlp_b1, D);
     if (rc) return fail(rc);
@@ -685,7 +733,9 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
     if (rc) return fail(rc);
     {
         const bool off = (cfg().disable_folds & DA_FOLD_MLP2) != 0;
-        if (!off && !mfma_disabled() && d->variant == DA_VARIANT_2D && d->hidden % 32 == 0 && d->arch != DA_ARCH_GCN) {
+        // (the discrete variant shares the body between the embedding and final_mlp.0, so it takes both folds; its K-wide head is the tail
+        //  kernel of da_d3pm.hip, which forms GELU(pre + sum_h pz_h) itself -- k_head_fold / k_tail_fused write at most 8 pose channels)
+        if (!off && !mfma_disabled() && (d->variant == DA_VARIANT_2D || discrete) && d->hidden % 32 == 0 && d->arch != DA_ARCH_GCN) {
             // compose in fp32 from the caller's fp32 weights, then pack
             const int hid = d->hidden, hc0 = d->conv[0].hc;
             float *w2t = (float *)alloc((size_t)hid * D * 4);                  // W2^T [hidden, D]
@@ -738,7 +788,7 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
             // last conv: value heads and skip folded with final_mlp.0
             const int L = d->n_layers - 1, hcL = d->conv[L].hc, CL = d->conv[L].C, dinL = d->conv[L].din;
             const bool off2 = (cfg().disable_folds & DA_FOLD_LAST) != 0;
-            if (!off2 && CL == 144 && hcL == D && dinL % 32 == 0 && d->c_out <= 8) {        // (k_head_fold: 8 outputs per row at most)
+            if (!off2 && CL == 144 && hcL == D && dinL % 32 == 0 && (d->c_out <= 8 || discrete)) {        // (k_head_fold: 8 outputs per row at most)
                 const int nf = 2 * hcL + H * 32;
                 float *lw = (float *)alloc((size_t)nf * dinL * 4);
                 float *sw = (float *)alloc((size_t)32 * dinL * 4);
@@ -856,6 +906,7 @@ int da_denoiser_forward(da_denoiser *d, const da_graph *g, const float *x, const
                         float *out, float *alpha, int alpha_all_layers, float *pre_head, void *workspace,
                         size_t workspace_bytes, void *stream) {
     DA_REQUIRE(d && g && x && out && workspace, "da_denoiser_forward: null argument");
+    DA_REQUIRE(d->variant != DA_VARIANT_DISCRETE, "da_denoiser_forward: a discrete denoiser takes position indices (da_denoiser_forward_idx)");
     int rc = check_graph(d, g);
     if (rc) return rc;
     DA_REQUIRE(!alpha || d->arch != DA_ARCH_GCN, "alpha requested from a GCN denoiser: GCN.forward returns no attention weights (gcn.py:22)");
@@ -869,6 +920,7 @@ int da_ddim_step(const da_schedule *s, int variant, int mean_type, int n, int c,
                  const float *model_out, const int64_t *t, int64_t t_scalar, int inference_ratio,
                  int prev_all_nonneg, float eta, const float *noise, float *x_prev, void *stream) {
     DA_REQUIRE(s && x && model_out && x_prev, "da_ddim_step: null argument");
+    DA_REQUIRE(variant != DA_VARIANT_DISCRETE, "da_ddim_step: the discrete variant has no pose update (da_d3pm_step)");
     DA_REQUIRE(eta == 0.f || noise, "da_ddim_step: eta > 0 needs noise");
     if (variant == DA_VARIANT_3D) {
         DA_REQUIRE(c == 7, "da_ddim_step(3D): c must be 7");
@@ -952,6 +1004,7 @@ int da_sample_loop_ex(da_denoiser *d, const da_graph *g, const da_schedule *s, i
                       int max_iters, const float *x_init, float *traj, float *x_final, void *workspace,
                       size_t workspace_bytes, int use_graph, const da_loop_opts *opts, void *stream) {
     DA_REQUIRE(d && g && s && x_init && workspace, "da_sample_loop: null argument");
+    DA_REQUIRE(d->variant != DA_VARIANT_DISCRETE, "da_sample_loop: a discrete denoiser samples position indices (da_sample_loop_idx)");
     da_loop_opts o;
     memset(&o, 0, sizeof(o));
     if (opts) { o.sampler = opts->sampler; o.eta = opts->eta; o.cfg = opts->cfg; o.cfg_w = opts->cfg_w; o.noise = opts->noise; }
@@ -1020,6 +1073,7 @@ int da_sample_loop_pair_ex(da_denoiser *d, const da_schedule *s, int mean_type, 
                            size_t noise_stride, void *stream) {
     DA_REQUIRE(d && s && g_a && g_b && x_init_a && x_init_b && x_final_a && x_final_b && workspace_a && workspace_b,
                "da_sample_loop_pair: null argument");
+    DA_REQUIRE(d->variant != DA_VARIANT_DISCRETE, "da_sample_loop_pair: a discrete denoiser samples position indices (da_sample_loop_idx)");
     // the samplers of da_sample_loop_ex on both branches: one option set, half a reads opts->noise, half b noise_b (row ranges
     // of one [n_iters, N, c] draw: the poses then equal the one-branch loop's bit for bit)
     da_loop_opts oa, ob;
@@ -1198,6 +1252,100 @@ int da_sample_loop_pair(da_denoiser *d, const da_schedule *s, int mean_type, int
                         void *stream) {
     return da_sample_loop_pair_traj(d, s, mean_type, inference_ratio, max_iters, g_a, x_init_a, x_final_a, workspace_a, workspace_a_bytes,
                                     g_b, x_init_b, x_final_b, workspace_b, workspace_b_bytes, nullptr, nullptr, 0, stream);
+}
+
+// ---------------------------------------------------------------------------------------- discrete (D3PM) variant
+int da_denoiser_forward_idx(da_denoiser *d, const da_graph *g, const int32_t *idx, const int64_t *t, int64_t t_scalar, float *logits,
+                            float *alpha, int alpha_all_layers, void *workspace, size_t workspace_bytes, void *stream) {
+    DA_REQUIRE(d && g && idx && logits && workspace, "da_denoiser_forward_idx: null argument");
+    DA_REQUIRE(d->variant == DA_VARIANT_DISCRETE, "da_denoiser_forward_idx: not a discrete denoiser (da_denoiser_forward takes poses)");
+    int rc = check_graph(d, g);
+    if (rc) return rc;
+    DA_REQUIRE(!alpha || g->edge_id, "alpha requested but graph has no edge_id");
+    Workspace w = carve(d, g, workspace);
+    DA_REQUIRE(workspace_bytes >= w.total, "workspace too small: %zu < %zu", workspace_bytes, w.total);
+    hipStream_t st = (hipStream_t)stream;
+    DiscreteIn di{idx, w.hh, (char *)w.pz, w.head_pre, 0};
+    if ((rc = forward_impl(d, g, nullptr, t, t_scalar, nullptr, alpha, alpha_all_layers, nullptr, w, st, nullptr, false, false, &di))) return rc;
+    const D3pmRows rows = di.rows();
+    return timed(d, DA_PROF_HEAD, st, [&] {
+        return launch_d3pm_tail(d->prec, g->n_real, d->c_out, d->heads, &rows, nullptr, 0.f, d->head_w1, d->head_b1, nullptr, logits, nullptr, st); });
+}
+
+static int enqueue_loop_idx(da_denoiser *d, const da_graph *g, const da_schedule *s, int ratio, int n_iters, const int32_t *idx_init,
+                            int32_t *traj, int32_t *idx_final, const Workspace &w, hipStream_t st, const da_d3pm_opts &o) {
+    // p_sample_loop, spatial_diffusion_discrete.py:324-356: for i in reversed(range(0, steps, ratio)): forward (two under guidance),
+    // categorical reverse step.  Per step: the embedding lookup, the shared denoiser body up to final_mlp.0, ONE tail kernel.
+    const int nr = g->n_real, K = d->c_out;
+    const int first = ((s->steps - 1) / ratio) * ratio;
+    const int32_t *cur = idx_init;
+    int it = 0, rc;
+    for (int i = first; i >= 0 && it < n_iters; i -= ratio, ++it) {
+        int32_t *nxt = traj ? traj + (size_t)it * nr : (int32_t *)((it & 1) ? w.xbuf1 : w.xbuf0);
+        DiscreteIn dc{cur, w.hh, (char *)w.pz, w.head_pre, 0}, du{cur, w.hh_unc, w.pz_unc, w.head_pre_unc, 0};
+        if ((rc = forward_impl(d, g, nullptr, nullptr, i, nullptr, nullptr, 0, nullptr, w, st, nullptr, false, false, &dc))) return rc;
+        if (o.cfg && (rc = forward_impl(d, g, nullptr, nullptr, i, nullptr, nullptr, 0, nullptr, w, st, nullptr, true, false, &du))) return rc;
+        D3pmStep sp;
+        sp.s = to_dev(s); sp.x_t = cur; sp.t_scalar = i; sp.ratio = ratio; sp.iteration = it; sp.x_prev = nxt; sp.seed = o.seed;
+        sp.noise = o.noise ? o.noise + (size_t)it * nr * K : nullptr;
+        const D3pmRows rc_ = dc.rows(), ru_ = du.rows();
+        if ((rc = timed(d, DA_PROF_UPDATE, st, [&] {
+                 return launch_d3pm_tail(d->prec, nr, K, d->heads, &rc_, o.cfg ? &ru_ : nullptr, o.cfg_w, d->head_w1, d->head_b1, nullptr, nullptr, &sp, st); }))) return rc;
+        cur = nxt;
+    }
+    if (idx_final && cur != idx_final) DA_CHECK_HIP(hipMemcpyAsync(idx_final, cur, (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int da_sample_loop_idx(da_denoiser *d, const da_graph *g, const da_schedule *s, int inference_ratio, int max_iters, const int32_t *idx_init,
+                       int32_t *traj, int32_t *idx_final, void *workspace, size_t workspace_bytes, int use_graph, const da_d3pm_opts *opts,
+                       void *stream) {
+    DA_REQUIRE(d && g && s && idx_init && workspace && opts, "da_sample_loop_idx: null argument");
+    DA_REQUIRE(d->variant == DA_VARIANT_DISCRETE, "da_sample_loop_idx: not a discrete denoiser (da_sample_loop takes poses)");
+    DA_REQUIRE(inference_ratio >= 1 && s->steps >= 1 && s->alphas_cumprod, "da_sample_loop_idx: bad ratio / schedule");
+    DA_REQUIRE(opts->noise || opts->seed, "da_sample_loop_idx: needs the uniforms (opts->noise) or a seed (opts->seed)");
+    da_d3pm_opts o;
+    memset(&o, 0, sizeof(o));
+    o.cfg = opts->cfg ? 1 : 0; o.cfg_w = opts->cfg ? opts->cfg_w : 0.f; o.noise = opts->noise; o.seed = opts->seed;
+    int rc = check_graph(d, g);
+    if (rc) return rc;
+    Workspace w = carve(d, g, workspace);
+    DA_REQUIRE(workspace_bytes >= w.total, "workspace too small: %zu < %zu", workspace_bytes, w.total);
+    hipStream_t st = (hipStream_t)stream;
+    const int total = (s->steps + inference_ratio - 1) / inference_ratio;
+    const int n_iters = (max_iters > 0 && max_iters < total) ? max_iters : total;
+    // the capture rules of da_sample_loop_ex: eager while profiling, straight into a capture the caller has open
+    if (d->prof_on || stream_is_capturing(st)) use_graph = 0;
+    if (!use_graph) return enqueue_loop_idx(d, g, s, inference_ratio, n_iters, idx_init, traj, idx_final, w, st, o);
+
+    LoopKey key;
+    memset(&key, 0, sizeof(key));
+    key.g = *g; key.s = *s; key.mean_type = -1 /* the discrete loop */; key.ratio = inference_ratio; key.max_iters = n_iters;
+    key.x_init = (const float *)idx_init; key.traj = (float *)traj; key.x_final = (float *)idx_final; key.ws = workspace; key.ws_bytes = workspace_bytes;
+    key.opts.cfg = o.cfg; key.opts.cfg_w = o.cfg_w; key.opts.noise = o.noise; key.seed = o.seed; key.cfg = cfg();
+    hipGraphExec_t exec = nullptr;
+    for (auto &e : d->loops)
+        if (memcmp(&key, &e.key, sizeof(key)) == 0) exec = e.exec;
+    if (!exec) {
+        if (d->loops.size() >= 8) {
+            (void)hipGraphExecDestroy(d->loops.front().exec);
+            d->loops.erase(d->loops.begin());
+        }
+        hipGraph_t graph = nullptr;
+        if (!d->cap_stream) DA_CHECK_HIP(hipStreamCreateWithFlags(&d->cap_stream, hipStreamNonBlocking));
+        hipStream_t cs = d->cap_stream;
+        DA_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed));
+        rc = enqueue_loop_idx(d, g, s, inference_ratio, n_iters, idx_init, traj, idx_final, w, cs, o);
+        hipError_t e = hipStreamEndCapture(cs, &graph);
+        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+        if (e != hipSuccess || !graph) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return 2; }
+        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (e != hipSuccess) { set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e)); return 2; }
+        d->loops.push_back({key, exec});
+    }
+    DA_CHECK_HIP(hipGraphLaunch(exec, st));
+    return 0;
 }
 
 size_t da_attn_dense_scratch_bytes(int prec, const da_graph *g, int heads, int C) {

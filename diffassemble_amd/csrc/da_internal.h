@@ -237,6 +237,31 @@ int launch_gcn_aggregate(int prec, const da_graph *g, int W, const float *dinv, 
 int launch_gcn_aggregate_t(int prec, const da_graph *g, int W, const float *dinv, const void *X, void *out, hipStream_t st);   // A_hat^T X
 int launch_gcn_gelu_res(size_t n, const float *pre, const float *res, float *out, hipStream_t st);                           // gelu(pre) + res
 
+// da_d3pm.hip: the discrete (D3PM) variant's embedding lookup and its tail (logits head + guidance + categorical reverse step)
+struct D3pmStep {
+    DeviceSchedule s = {};
+    const int32_t *x_t = nullptr;
+    const int64_t *t = nullptr;
+    int64_t t_scalar = 0;
+    int ratio = 1;
+    const float *noise = nullptr;        // [n, K] uniforms of this iteration, or NULL: drawn from `seed`
+    const uint64_t *seed = nullptr;      // device {seed, offset}
+    int iteration = 0;
+    int32_t *x_prev = nullptr;
+    float *post = nullptr;               // nullable [n, K]: the posterior logits before the Gumbel term
+};
+int launch_embed_idx_time(int prec, int n, int K, int F, int D, const int32_t *idx, const int64_t *t, int64_t t_scalar, int steps,
+                          const float *time_emb, const float *pos_emb, void *comb_in, hipStream_t st);
+// where a pass left its final_mlp.0 rows: post-GELU `hh` [n, 32], or (last-layer fold) the per-head outputs `pz` [H, n, 32] of the folded
+// attention with the pre-activation addend `pre` [n, 32] -- hh = GELU(pre + sum_h pz_h), summed in k_head_fold's order; act dtype
+struct D3pmRows {
+    const void *hh = nullptr, *pz = nullptr, *pre = nullptr;
+};
+// logits from the conditional rows (and the unconditional ones under guidance) through w2 / b2, or given (logits_in: rows_c may be
+// NULL); logits_out nullable; step == NULL: logits only
+int launch_d3pm_tail(int prec, int n, int K, int H, const D3pmRows *rows_c, const D3pmRows *rows_u, float cfg_w, const float *w2,
+                     const float *b2, const float *logits_in, float *logits_out, const D3pmStep *step, hipStream_t st);
+
 // generic linear dispatch (MFMA when the shape allows, else simple)
 int linear(int prec, int M, int K, int Nout, const void *A, int lda, const void *W, const float *bias, int act,
            const void *res, void *out, int ldo, hipStream_t st);

@@ -42,6 +42,12 @@ class Schedule:
         return self._trap
 
 
+def _wrap64(v):
+    """A Python int as the two's-complement int64 that carries the same 64 bits."""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
 IGSO3_SAMPLES = 1000      # angle samples of IsotropicGaussianSO3 (distributions.py:491); a CDF row has one entry less
 
 
@@ -84,8 +90,8 @@ def igso3_trap_table(sqrt_one_minus_alphas_cumprod):
 
 
 class DenoiserEngine:
-    """Packs an ``Eff_GAT`` / ``Eff_GAT_3d`` state dict (reference key layout, see
-    the key list in DESIGN.md section 1) into the HIP library and runs forward / sampling on it."""
+    """Packs an ``Eff_GAT`` / ``Eff_GAT_3d`` / ``Eff_GAT_Discrete`` (``variant="discrete"``) state dict (reference key layout,
+    see the key list in DESIGN.md section 1) into the HIP library and runs forward / sampling on it."""
 
     def __init__(self, sd, *, variant="2d", arch="transformer", virt_nodes=0, precision="bf16",
                  device=None):
@@ -109,16 +115,20 @@ class DenoiserEngine:
         self.n_layers = len(layers)
         D = sd["mlp.0.weight"].shape[1]
         self.D, self.F = D, D - 64
-        self.c_in = sd["pos_mlp.0.weight"].shape[1]
+        discrete = variant == "discrete"          # Eff_GAT_Discrete: pos_mlp is an Embedding(K, 32), the head is K wide
+        self.c_in = 1 if discrete else sd["pos_mlp.0.weight"].shape[1]
         self.steps = sd["time_emb.weight"].shape[0]
-        w.variant = _lib.VARIANT_3D if variant == "3d" else _lib.VARIANT_2D
+        w.variant = {"3d": _lib.VARIANT_3D, "discrete": _lib.VARIANT_DISCRETE}.get(variant, _lib.VARIANT_2D)
         w.arch = {"exophormer": _lib.ARCH_EXOPHORMER, "gcn": _lib.ARCH_GCN}.get(arch, _lib.ARCH_TRANSFORMER)
         w.steps, w.c_in, w.feat_dim = self.steps, self.c_in, self.F
         w.hidden = sd["mlp.0.weight"].shape[0]
         w.heads, w.n_layers, w.virt_nodes = 8, self.n_layers, self.virt_nodes
         w.time_emb = P("time_emb.weight")
-        w.pos_w0, w.pos_b0 = P("pos_mlp.0.weight"), P("pos_mlp.0.bias")
-        w.pos_w1, w.pos_b1 = P("pos_mlp.2.weight"), P("pos_mlp.2.bias")
+        if discrete:
+            w.pos_w1 = P("pos_mlp.weight")                 # [K, 32]; pos_w0 / pos_b0 / pos_b1 stay NULL (da_weights, DA_VARIANT_DISCRETE)
+        else:
+            w.pos_w0, w.pos_b0 = P("pos_mlp.0.weight"), P("pos_mlp.0.bias")
+            w.pos_w1, w.pos_b1 = P("pos_mlp.2.weight"), P("pos_mlp.2.bias")
         w.mlp_w0, w.mlp_b0 = P("mlp.0.weight"), P("mlp.0.bias")
         w.mlp_w1, w.mlp_b1 = P("mlp.2.weight"), P("mlp.2.bias")
         for l in layers:
@@ -156,6 +166,8 @@ class DenoiserEngine:
         self._ws = {}
         self._loop_bufs = {}
         self._pair_state = None            # two-branch loop: half plans, workspaces, pose buffers
+        self.K = self.c_out if discrete else None
+        self._seed = None                  # discrete loop: the persistent 16-byte {seed, offset} tensor the captured kernels read
         self._profiling = False
 
     def __del__(self):
@@ -249,13 +261,15 @@ class DenoiserEngine:
             tt, ts = None, int(t)
             nonneg = int(ts - ratio >= 0)
         nz = None if noise is None else _f32(noise, self.device)
-        variant = _lib.VARIANT_3D if self.variant == "3d" else _lib.VARIANT_2D
+        variant = {"3d": _lib.VARIANT_3D, "discrete": _lib.VARIANT_DISCRETE}.get(self.variant, _lib.VARIANT_2D)
         _lib.check(self.lib.da_ddim_step(C.byref(sched.c), variant, mean_type, x.shape[0], x.shape[1],
                                          _lib.ptr(x), _lib.ptr(model_out), _lib.ptr(tt), ts, int(ratio), nonneg,
                                          float(eta), _lib.ptr(nz), _lib.ptr(out), _lib.stream_ptr(self.device)))
         return out
 
     def ddpm_step(self, sched: Schedule, x, model_out, t, noise=None):
+        if self.variant == "discrete":      # (da_ddpm_step takes neither a denoiser nor a variant: refused here)
+            raise _lib.DaError("ddpm_step: the discrete variant has no pose update (d3pm_step)")
         x, model_out = _f32(x, self.device), _f32(model_out, self.device)
         out = torch.empty_like(x)
         if torch.is_tensor(t):
@@ -332,6 +346,81 @@ class DenoiserEngine:
             int(bool(use_graph)), _lib.stream_ptr(self.device)))
         return traj, x_final
 
+
+    # ------------------------------------------------------------------ discrete (D3PM) variant
+    def _tt(self, t):
+        if torch.is_tensor(t):
+            return t.to(device=self.device, dtype=torch.int64).contiguous(), 0
+        return None, int(t)
+
+    def _i32(self, x):
+        return x.detach().to(device=self.device, dtype=torch.int32).contiguous()
+
+    def forward_idx(self, plan, idx, t, feats=None, return_alpha=False):
+        """Eff_GAT_Discrete.forward_with_feats: position indices [N] (any integer dtype) -> logits [N, K] fp32
+        (da_denoiser_forward_idx).  ``feats=None`` reuses the staged features; ``return_alpha`` adds every layer's [E, 8]."""
+        if return_alpha:
+            plan.ensure_csr()
+        g, ws = self.set_features(plan, feats) if feats is not None else self._workspace(plan)
+        idx = self._i32(idx)
+        out = torch.empty((plan.n_real, self.c_out), dtype=torch.float32, device=self.device)
+        alpha = torch.empty((self.n_layers, plan.n_edges, 8), dtype=torch.float32, device=self.device) if return_alpha else None
+        tt, ts = self._tt(t)
+        _lib.check(self.lib.da_denoiser_forward_idx(self.handle, C.byref(g), _lib.ptr(idx), _lib.ptr(tt), ts, _lib.ptr(out), _lib.ptr(alpha),
+                                                    1, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(self.device)))
+        return (out, alpha) if return_alpha else out
+
+    def seed_tensor(self, seed=None, offset=0, generator=None):
+        """The engine's persistent {seed, offset} pair (int64 [2] on the device, read by the step kernels), refilled: from ``seed`` /
+        ``offset`` when given, else by one draw from ``generator`` or torch's default generator."""
+        if self._seed is None:
+            self._seed = torch.zeros(2, dtype=torch.int64, device=self.device)
+        if seed is None and generator is not None and generator.device.type == "cpu":
+            self._seed.copy_(torch.empty(2, dtype=torch.int64).random_(generator=generator))
+        elif seed is None:
+            self._seed.random_(generator=generator)
+        else:
+            self._seed.copy_(torch.tensor([_wrap64(seed), _wrap64(offset)], dtype=torch.int64))
+        return self._seed
+
+    def d3pm_noise(self, seed, iteration, n, K):
+        return d3pm_noise(seed, iteration, n, K)
+
+    def d3pm_step(self, sched: Schedule, x_t, logits, t, ratio, noise=None, seed=None, iteration=0, return_post=False):
+        return d3pm_step(sched, x_t, logits, t, ratio, noise=noise, seed=seed, iteration=iteration, return_post=return_post)
+
+    def sample_loop_idx(self, plan, sched: Schedule, idx_init, feats, *, ratio=1, max_iters=0, keep_traj=True, use_graph=True,
+                        cfg_w=None, noise=None, generator=None, restage=True):
+        """The discrete p_sample_loop in one C call (da_sample_loop_idx; one hipGraph launch when ``use_graph``).  Returns
+        (traj [n_iters, N] int32 or None, idx_final [N] int32): engine-owned buffers the next call of the same shape overwrites.
+        The Gumbel uniforms come from the kernels' own generator, keyed by the engine's persistent seed tensor, which is refilled
+        from ``generator`` (or torch's default generator) before every launch; ``noise`` [n_iters, N, K] injects them instead."""
+        total = (sched.steps + ratio - 1) // ratio
+        n_iters = min(max_iters, total) if max_iters and max_iters > 0 else total
+        g, ws = self.set_features(plan, feats) if restage else self._workspace(plan)
+        key = ("idx", plan.n_real, n_iters, bool(keep_traj))
+        bufs = self._loop_bufs.get(key)
+        if bufs is None:
+            xi = torch.empty(plan.n_real, dtype=torch.int32, device=self.device)
+            traj = torch.empty((n_iters, plan.n_real), dtype=torch.int32, device=self.device) if keep_traj else None
+            bufs = self._loop_bufs[key] = (xi, traj, torch.empty_like(xi))
+        xi, traj, x_final = bufs
+        xi.copy_(idx_init)
+        self._loop_keep = plan
+        o = _lib.DaD3pmOpts()
+        o.cfg, o.cfg_w = (0, 0.0) if cfg_w is None else (1, float(cfg_w))
+        if noise is not None:
+            nb = self._loop_bufs.get(("unoise",) + key)
+            if nb is None:
+                nb = self._loop_bufs[("unoise",) + key] = torch.empty((n_iters, plan.n_real, self.c_out), dtype=torch.float32, device=self.device)
+            nb.copy_(noise)
+            o.noise = nb.data_ptr()
+        else:
+            o.seed = self.seed_tensor(generator=generator).data_ptr()
+        _lib.check(self.lib.da_sample_loop_idx(self.handle, C.byref(g), C.byref(sched.c), int(ratio), int(n_iters), _lib.ptr(xi),
+                                               _lib.ptr(traj), _lib.ptr(x_final), _lib.ptr(ws), ws.numel(), int(bool(use_graph)),
+                                               C.byref(o), _lib.stream_ptr(self.device)))
+        return traj, x_final
 
     # ------------------------------------------------------------------ two-branch loop
     two_branch_min_nodes = 40000       # DA_TWO_BRANCH=auto: the pair loop from this many pieces per Batch
@@ -489,6 +578,38 @@ class DenoiserEngine:
 
 
 # ---------------------------------------------------------------------- kernel-level helpers
+def d3pm_noise(seed, iteration, n, K):
+    """The uniforms the discrete reverse step draws for itself from ``seed`` (int64 [2] device tensor {seed, offset}): [n, K] fp32
+    in (0, 1] (da_d3pm_noise)."""
+    u = torch.empty((n, K), dtype=torch.float32, device=seed.device)
+    with torch.cuda.device(seed.device):
+        _lib.check(_lib.lib().da_d3pm_noise(_lib.ptr(seed), int(iteration), int(n), int(K), _lib.ptr(u), _lib.stream_ptr(seed.device)))
+    return u
+
+
+def d3pm_step(sched: Schedule, x_t, logits, t, ratio, noise=None, seed=None, iteration=0, return_post=False):
+    """p_sample_ddpm after the model call (da_d3pm_step, spatial_diffusion_discrete.py:282-320): x_t [N] indices, logits [N, K] fp32
+    on a ROCm device -> x_{t - ratio} [N] int64 (and the posterior logits [N, K] before the Gumbel term with ``return_post``).
+    ``noise`` [N, K] uniforms, or ``seed`` (int64 [2] device tensor) for the kernel's own draw; t: int64 [N] tensor or python int."""
+    dev = logits.device
+    if dev.type != "cuda":
+        raise _lib.DaError("d3pm_step needs ROCm tensors (no CPU path in diffassemble_amd)")
+    x_t, logits = x_t.detach().to(device=dev, dtype=torch.int32).contiguous(), _f32(logits, dev)
+    n, K = logits.shape
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    post = torch.empty_like(logits) if return_post else None
+    nz = None if noise is None else _f32(noise, dev)
+    if torch.is_tensor(t):
+        tt, ts = t.to(device=dev, dtype=torch.int64).contiguous(), 0
+    else:
+        tt, ts = None, int(t)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().da_d3pm_step(C.byref(sched.c), n, K, _lib.ptr(x_t), _lib.ptr(logits), _lib.ptr(tt), ts, int(ratio),
+                                           _lib.ptr(nz), _lib.ptr(seed), int(iteration), _lib.ptr(out), _lib.ptr(post),
+                                           _lib.stream_ptr(dev)))
+    return (out.long(), post) if return_post else out.long()
+
+
 def linear(x, weight, bias=None, act=_lib.ACT_NONE, residual=None, precision="fp32"):
     """out = act(x @ weight^T + bias) + residual through da_linear (x, weight: [M,K], [N,K])."""
     prec = _PREC[precision]

@@ -1,9 +1,10 @@
 """Counterpart of puzzle_diff/model/backbones/__init__.py:1-8 (minus the import of the
-missing ``backbone_vist`` file).  The hot-path denoisers are real; the ablation
-architectures the drivers merely import are placeholders that fail on construction
-(out of scope)."""
+missing ``backbone_vist`` file).  The hot-path denoisers are real (``Eff_GAT_Discrete``:
+inference only); the ablation architectures the drivers merely import are placeholders that
+fail on construction (out of scope)."""
 from .efficient_gat import Eff_GAT
 from .efficient_gat_3d import Eff_GAT_3d
+from .efficient_gat_discrete import Eff_GAT_Discrete
 from .exophormer_gnn import Exophormer_GNN
 from .gcn import GCN, GCNConv
 from .Transformer_GNN import Transformer_GNN
@@ -21,7 +22,6 @@ def _out_of_scope(name):
 
 
 Dark_TFConv = _out_of_scope("Dark_TFConv")
-Eff_GAT_Discrete = _out_of_scope("Eff_GAT_Discrete")
 Eff_GAT_Discrete_ROT = _out_of_scope("Eff_GAT_Discrete_ROT")
 Eff_GAT_Vist = _out_of_scope("Eff_GAT_Vist")
 

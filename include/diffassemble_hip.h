@@ -31,7 +31,8 @@ extern "C" {
 #define DA_ABI_VERSION 19
 
 enum { DA_PREC_F32 = 0, DA_PREC_BF16 = 1 };
-enum { DA_VARIANT_2D = 0, DA_VARIANT_3D = 1 };          /* Eff_GAT / Eff_GAT_3d            */
+enum { DA_VARIANT_2D = 0, DA_VARIANT_3D = 1,             /* Eff_GAT / Eff_GAT_3d            */
+       DA_VARIANT_DISCRETE = 2 };                        /* Eff_GAT_Discrete (below)        */
 enum { DA_ARCH_TRANSFORMER = 0, DA_ARCH_EXOPHORMER = 1, /* GELU between convs / none      */
        DA_ARCH_GCN = 2 };                                /* two GCNConv, GELU after each    */
 enum { DA_MEAN_EPSILON = 0, DA_MEAN_START_X = 1 };       /* spatial_diffusion.py:63-66      */
@@ -84,6 +85,13 @@ int da_build_flags(void);        /* bit 0: EXPERIMENTS build                    
  * DA_ARCH_GCN replaces the GCN of backbones/gcn.py:5-22 (efficient_gat.py:65-70, efficient_gat_3d.py:114-119):
  * n_layers = 2, conv_wq[l] = module_list.l.lin.weight ([256, D] / [D, 256]), conv_bq[l] = module_list.l.bias
  * ([256] / [D]); the other conv pointers, heads and virt_nodes are not read.
+ * DA_VARIANT_DISCRETE replaces Eff_GAT_Discrete (backbones/efficient_gat_discrete.py:19-51), the denoiser of the discrete position
+ * diffusion: the 2D transformer body between an embedding lookup and a K-wide logits head.  c_in = 1 (one position index per
+ * piece), c_out = K with 2 <= K <= 1024, arch = DA_ARCH_TRANSFORMER, pos_w1 = pos_mlp.weight [K, 32] (pos_w0 / pos_b0 / pos_b1
+ * are NULL and not read), head_w1 / head_b1 = final_mlp.2 [K, 32] / [K]; da_denoiser_create checks all of it.  A discrete
+ * denoiser is driven through da_denoiser_forward_idx / da_sample_loop_idx; every entry that takes float poses
+ * (da_denoiser_forward, da_sample_loop*, da_ddim_step with this variant) REJECTS it with a da_last_error message and launches
+ * nothing (da_ddpm_step takes neither a denoiser nor a variant: the host layer refuses it).  The layout of this struct is unchanged.
  * ------------------------------------------------------------------------------------- */
 typedef struct da_weights {
     int32_t variant;      /* DA_VARIANT_*                                                  */
@@ -336,6 +344,62 @@ int da_sample_loop_pair_ex(da_denoiser *d, const da_schedule *s, int mean_type, 
                            void *workspace_b, size_t workspace_b_bytes,
                            float *traj_a, float *traj_b, size_t traj_stride,
                            const da_loop_opts *opts, const float *noise_b, size_t noise_stride, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Discrete position diffusion (D3PM with the uniform transition; model/spatial_diffusion_discrete.py over
+ * backbones/efficient_gat_discrete.py).  Pieces carry a position INDEX in [0, K); the denoiser returns K logits per piece.
+ *
+ * The reference stores Q_onestep, its transpose and overline_Q as [steps, K, K] fp32 tables and calls torch.linalg.inv on a
+ * [N, K, K] batch per sampling step (:68-82, :209-212).  For Q_t = (1 - beta_t) I + beta_t / K 11^T these have a closed form:
+ * overline_Q[t] = a_t I + (1 - a_t) / K 11^T with a_t = alphas_cumprod[t], and for p < t
+ * overline_Q[t] overline_Q[p]^-1 = r I + (1 - r) / K 11^T with r = a_t / a_p.  The library evaluates that form in fp32 from
+ * da_schedule.alphas_cumprod: no K x K object exists (documented deviation: the reference's fp32 matrix products and inverse
+ * lose digits the closed form keeps).
+ * ------------------------------------------------------------------------------------- */
+/* One denoiser forward == Eff_GAT_Discrete.forward_with_feats (efficient_gat_discrete.py:72-97), encoder bypassed.
+ *   idx    [n_real] int32 position indices; values outside [0, K) are clamped (as t is)
+ *   t      [n_real] int64 or NULL => t_scalar;  logits [n_real, K] fp32;  alpha as da_denoiser_forward                    */
+int da_denoiser_forward_idx(da_denoiser *d, const da_graph *g, const int32_t *idx, const int64_t *t, int64_t t_scalar,
+                            float *logits, float *alpha, int alpha_all_layers, void *workspace, size_t workspace_bytes,
+                            void *stream);
+
+/* The categorical reverse step == p_sample_ddpm after the model call (spatial_diffusion_discrete.py:282-320) with
+ * q_posterior_logits (:193-227).  With p = t - inference_ratio and pi = softmax(logits):
+ *   t == 0 : x_prev = argmax_k logits[k]                                  (no posterior, no noise)
+ *   t  > 0 : post[k] = log(r [k == x_t] + (1 - r) / K + 1e-8) + log(a_p pi[k] + (1 - a_p) / K + 1e-8)
+ *            x_prev  = argmax_k (post[k] - log(-log(clip(u[k], FLT_MIN, 1))))     the lowest index wins a tie
+ *   x_t [n] int32, logits [n, K] fp32, t per node or NULL => t_scalar, x_prev [n] int32; 2 <= K <= 1024.
+ *   noise  [n, K] fp32 uniforms, or NULL: the step draws them itself from `seed` (device, {seed, offset}; da_d3pm_noise)
+ *   post   NULL or [n, K] fp32: post[] before the Gumbel term (the logits where t == 0), for tests
+ * A scalar t with 0 < t < inference_ratio is an error (t - ratio < 0 has no posterior; the reference's loop never asks for it);
+ * with per-node t the same condition is a precondition the caller keeps (such a row is evaluated with p = 0).           */
+int da_d3pm_step(const da_schedule *s, int n, int K, const int32_t *x_t, const float *logits, const int64_t *t,
+                 int64_t t_scalar, int inference_ratio, const float *noise, const uint64_t *seed, int iteration,
+                 int32_t *x_prev, float *post, void *stream);
+
+/* The uniforms da_d3pm_step / da_sample_loop_idx draw when no noise buffer is given, written out (same device function):
+ * Philox4x32-10, key = the two halves of seed[0], counter = (r K + k + seed[1] as 64 bits, iteration, a constant),
+ * u = ((bits >> 8) + 1) 2^-24 in (0, 1].  u [n, K] fp32.                                                                  */
+int da_d3pm_noise(const uint64_t *seed, int iteration, int n, int K, float *u, void *stream);
+
+/* The whole discrete sampling loop == p_sample_loop (spatial_diffusion_discrete.py:324-356): for i in reversed(range(0, steps,
+ * ratio)): forward (a second one over zero piece features under classifier-free guidance, logits = (1 + w) cond - w uncond,
+ * :285-300) and the reverse step, the K-wide head, guidance, softmax, posterior, Gumbel term and argmax in ONE kernel per step
+ * (the [n_real, K] logits never reach memory).  idx_init [n_real] int32; traj (nullable) [n_iters, n_real] int32 receives every
+ * step's indices, idx_final (nullable) the last.  Same hipGraph cache and capture rules as da_sample_loop_ex: recorded once,
+ * keyed on the arguments, eager while profiling, enqueued directly when the caller is capturing `stream`.
+ *   opts->noise  [n_iters, n_real, K] uniforms (parity tests), or NULL: drawn from opts->seed with iteration = the loop index
+ *   opts->seed   device {seed, offset}, read BY THE KERNELS: a replayed graph draws fresh numbers once the host has rewritten
+ *                those 16 bytes.  One of noise / seed is required.                                                        */
+typedef struct da_d3pm_opts {
+    int32_t cfg;          /* != 0: classifier-free guidance                                           */
+    float cfg_w;          /* classifier_free_w                                                        */
+    const float *noise;   /* [n_iters, n_real, K] or NULL                                             */
+    const uint64_t *seed; /* device {seed, offset} or NULL                                            */
+} da_d3pm_opts;
+int da_sample_loop_idx(da_denoiser *d, const da_graph *g, const da_schedule *s, int inference_ratio, int max_iters,
+                       const int32_t *idx_init, int32_t *traj, int32_t *idx_final, void *workspace, size_t workspace_bytes,
+                       int use_graph, const da_d3pm_opts *opts, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Measurement aid (no reference counterpart: the reference has no profiler hooks).
