@@ -120,8 +120,9 @@ struct da_denoiser {
     std::vector<hipEvent_t> prof_ev;      // pairs (start, stop)
     std::vector<int> prof_cls;
     size_t prof_used = 0;
-    // cached sampling-loop graphs (a few distinct loops, e.g. a full loop and a remainder)
-    struct LoopEntry { LoopKey key; hipGraphExec_t exec; };
+    // cached sampling-loop graphs (a few distinct loops, e.g. a full loop and a remainder), oldest first.  One entry type for both caches:
+    // a one-branch loop leaves `b` zero and `exec_b` null; a pair loop in split mode keeps its second branch as a graph of its own in `exec_b`
+    struct LoopEntry { LoopKey a, b; hipGraphExec_t exec, exec_b; };
     std::vector<LoopEntry> loops;
     hipStream_t cap_stream = nullptr;     // private stream used only to RECORD graphs (the caller's
                                           // stream may be the legacy null stream, which cannot capture)
@@ -136,8 +137,7 @@ struct da_denoiser {
     // da_sample_loop_pair: the second branch of the two-branch loop graph
     hipStream_t pair_stream = nullptr;
     hipEvent_t ev_pair_fork = nullptr, ev_pair_join = nullptr;
-    struct PairEntry { LoopKey a, b; hipGraphExec_t exec; hipGraphExec_t exec_b; };      // exec_b: the second branch as a graph of its own (split mode), else null
-    std::vector<PairEntry> pair_loops;
+    std::vector<LoopEntry> pair_loops;
 };
 
 namespace da {
@@ -504,8 +504,10 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
                     //  buys -- the scripted 8-puzzle Batch: 0.165 -> 0.152 ms per step, profiles/r06/r06_scripted_side_stream_variants.log)
                     if (d->side_stream && !d->prof_on && n > nr && g->n_real >= 8192) {
                         // fork: virtual rows on the side stream, real rows here, join before the next projection
+                        StreamJoin side_guard;      // the error exits below still join the side stream (a capture of `st` must not be left forked)
                         DA_CHECK_HIP(hipEventRecord(d->ev_fork, st));
                         DA_CHECK_HIP(hipStreamWaitEvent(d->side_stream, d->ev_fork, 0));
+                        side_guard.arm(d->side_stream, st, d->ev_join);
                         rc = launch_attn_csr_cont(prec, n, nr, g->agg_row_ptr ? g->agg_row_ptr : g->irr_row_ptr, g->agg_row_ptr ? g->agg_col_src : g->irr_col_src,
                                                   g->row_map, d->heads, c.C, g->n_pad, L, resid, act, dst, d->side_stream, g->agg_row_ptr ? g->agg_mult : nullptr);
                         if (rc) return rc < 0 ? 1 : rc;
@@ -514,6 +516,7 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
                                                g->pad_ptr, 0, resid, act, dst, st, &mk);
                         if (rc) return rc < 0 ? 1 : rc;
                         DA_CHECK_HIP(hipStreamWaitEvent(st, d->ev_join, 0));
+                        side_guard.armed = false;   // joined above: ev_join was recorded behind the rows' kernel, before the real rows' launch
                         xin = dst; ldx = c.hc;
                         continue;
                     }
@@ -582,6 +585,115 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
 __global__ void k_pair_delay(unsigned long long ticks) {
     const unsigned long long t0 = wall_clock64();
     while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
+}
+
+// ---------------------------------------------------------------------------------------- recording and caching the loops' graphs
+//  Every loop entry point validates its arguments, builds a LoopKey, and either replays the cached graph of that key or
+// records one: record_graph is the only place that captures, loop_key the only place that builds a key, cache_find / cache_insert the
+// only cache policy, and every fork of a library-owned stream sits under a StreamJoin.
+
+static int loop_iters(const da_schedule *s, int ratio, int max_iters) {
+    const int total = (s->steps + ratio - 1) / ratio;
+    return (max_iters > 0 && max_iters < total) ? max_iters : total;
+}
+
+// the caller's da_loop_opts (NULL = the plain DDIM loop) copied field by field into a zeroed struct -- it becomes part of a LoopKey -- and checked
+static int loop_opts(const char *who, const da_denoiser *d, const da_loop_opts *opts, da_loop_opts *o) {
+    memset(o, 0, sizeof(*o));
+    if (opts) { o->sampler = opts->sampler; o->eta = opts->eta; o->cfg = opts->cfg; o->cfg_w = opts->cfg_w; o->noise = opts->noise; }
+    DA_REQUIRE(o->sampler == 0 || o->sampler == 1, "%s: sampler must be 0 (DDIM) or 1 (DDPM)", who);
+    DA_REQUIRE(!(o->sampler == 1 || o->eta > 0.f) || o->noise, "%s: eta > 0 / DDPM need the noise buffer", who);
+    DA_REQUIRE(d->variant == DA_VARIANT_2D || (!o->cfg && o->sampler == 0 && o->eta == 0.f), "%s: the 3D loop has no guidance / stochastic variant", who);
+    return 0;
+}
+
+// Everything a recorded graph has baked in.  memset, then assign: keys are compared with memcmp, padding included.
+static LoopKey loop_key(const da_graph *g, const da_schedule *s, int mean_type, int ratio, int n_iters, const void *x_init, void *traj,
+                        void *x_final, void *ws, size_t ws_bytes, const da_loop_opts &o, size_t traj_stride = 0, size_t noise_stride = 0,
+                        const void *seed = nullptr) {
+    LoopKey k;
+    memset(&k, 0, sizeof(k));
+    k.g = *g; k.s = *s; k.mean_type = mean_type; k.ratio = ratio; k.max_iters = n_iters;
+    k.x_init = (const float *)x_init; k.traj = (float *)traj; k.x_final = (float *)x_final; k.ws = ws; k.ws_bytes = ws_bytes;
+    k.opts = o; k.traj_stride = traj ? traj_stride : 0; k.noise_stride = o.noise ? noise_stride : 0;
+    k.cfg = cfg(); k.seed = seed;
+    return k;
+}
+static const LoopKey no_key = {};           // the `b` of a one-branch entry (static storage: zero, padding included)
+
+// two_graphs: a pair entry matches only in the form (da_config.pair_split) it was recorded in
+static const da_denoiser::LoopEntry *cache_find(const std::vector<da_denoiser::LoopEntry> &c, const LoopKey &a, const LoopKey &b, bool two_graphs) {
+    const da_denoiser::LoopEntry *hit = nullptr;
+    for (const auto &e : c)
+        if (memcmp(&a, &e.a, sizeof(a)) == 0 && memcmp(&b, &e.b, sizeof(b)) == 0 && (e.exec_b != nullptr) == two_graphs) hit = &e;
+    return hit;
+}
+// small LRU-less caches: a full one drops its oldest entry
+static void cache_insert(std::vector<da_denoiser::LoopEntry> &c, size_t capacity, const da_denoiser::LoopEntry &e) {
+    if (c.size() >= capacity) {
+        (void)hipGraphExecDestroy(c.front().exec);
+        if (c.front().exec_b) (void)hipGraphExecDestroy(c.front().exec_b);
+        c.erase(c.begin());
+    }
+    c.push_back(e);
+}
+
+// enqueue(cs) -> 0 recorded on the library's capture stream into *out.  The capture is ended and the hipGraph_t destroyed on every path; a
+// non-zero rc of the callback comes back unchanged (its message stands), a capture / instantiate failure is 2.
+template <typename F>
+static int record_graph(da_denoiser *d, const char *what, F &&enqueue, hipGraphExec_t *out) {
+    *out = nullptr;
+    if (!d->cap_stream) DA_CHECK_HIP(hipStreamCreateWithFlags(&d->cap_stream, hipStreamNonBlocking));
+    hipStream_t cs = d->cap_stream;
+    hipGraph_t graph = nullptr;
+    DA_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed));
+    const int rc = enqueue(cs);
+    const hipError_t e_end = hipStreamEndCapture(cs, &graph);
+    const bool captured = e_end == hipSuccess && graph;
+    hipError_t e_inst = hipSuccess;
+    if (!rc && captured) e_inst = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (rc) return rc;
+    if (!captured) { set_error("%s: hipStreamEndCapture failed: %s", what, hipGetErrorString(e_end)); return 2; }
+    if (e_inst != hipSuccess || !*out) { *out = nullptr; set_error("%s: hipGraphInstantiate failed: %s", what, hipGetErrorString(e_inst)); return 2; }
+    return 0;
+}
+
+// a one-branch loop: replay the graph cached under `key`, recording it first if there is none
+template <typename F>
+static int launch_loop_graph(da_denoiser *d, const char *what, const LoopKey &key, F &&enqueue, hipStream_t st) {
+    const da_denoiser::LoopEntry *hit = cache_find(d->loops, key, no_key, false);
+    hipGraphExec_t exec = hit ? hit->exec : nullptr;
+    if (!exec) {
+        const int rc = record_graph(d, what, enqueue, &exec);
+        if (rc) return rc;
+        cache_insert(d->loops, 8, {key, no_key, exec, nullptr});       // eight: four Batches in flight x two loop lengths
+    }
+    DA_CHECK_HIP(hipGraphLaunch(exec, st));
+    return 0;
+}
+
+static int ensure_pair_stream(da_denoiser *d) {
+    if (d->pair_stream) return 0;
+    // DA_PAIR_PRIO (experiment, default 0): 1 = the pair stream at the device's highest priority, -1 = at its lowest -- a standing
+    // asymmetry between the branches (one takes free slots first, the other fills its tails) instead of two equals in lockstep
+    const int prio = DA_XENV("DA_PAIR_PRIO", 0);
+    if (prio) {
+        int lo = 0, hi = 0;                                                     // lo = numerically greatest = lowest priority
+        DA_CHECK_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
+        DA_CHECK_HIP(hipStreamCreateWithPriority(&d->pair_stream, hipStreamNonBlocking, prio > 0 ? hi : lo));
+    } else
+        DA_CHECK_HIP(hipStreamCreateWithFlags(&d->pair_stream, hipStreamNonBlocking));
+    DA_CHECK_HIP(hipEventCreateWithFlags(&d->ev_pair_fork, hipEventDisableTiming));
+    DA_CHECK_HIP(hipEventCreateWithFlags(&d->ev_pair_join, hipEventDisableTiming));
+    return 0;
+}
+// the pair stream behind everything enqueued on `us` so far; `join` brings it back into `us` on every exit of the caller's scope
+static int fork_pair_stream(da_denoiser *d, hipStream_t us, StreamJoin &join) {
+    DA_CHECK_HIP(hipEventRecord(d->ev_pair_fork, us));
+    DA_CHECK_HIP(hipStreamWaitEvent(d->pair_stream, d->ev_pair_fork, 0));     // (under a capture of `us`: the pair stream joins the capture)
+    join.arm(d->pair_stream, us, d->ev_pair_join);
+    return 0;
 }
 
 extern "C" {
@@ -1006,54 +1118,23 @@ int da_sample_loop_ex(da_denoiser *d, const da_graph *g, const da_schedule *s, i
     DA_REQUIRE(d && g && s && x_init && workspace, "da_sample_loop: null argument");
     DA_REQUIRE(d->variant != DA_VARIANT_DISCRETE, "da_sample_loop: a discrete denoiser samples position indices (da_sample_loop_idx)");
     da_loop_opts o;
-    memset(&o, 0, sizeof(o));
-    if (opts) { o.sampler = opts->sampler; o.eta = opts->eta; o.cfg = opts->cfg; o.cfg_w = opts->cfg_w; o.noise = opts->noise; }
-    DA_REQUIRE(o.sampler == 0 || o.sampler == 1, "da_sample_loop_ex: sampler must be 0 (DDIM) or 1 (DDPM)");
-    DA_REQUIRE(!(o.sampler == 1 || o.eta > 0.f) || o.noise, "da_sample_loop_ex: eta > 0 / DDPM need the noise buffer");
-    DA_REQUIRE(d->variant == DA_VARIANT_2D || (!o.cfg && o.sampler == 0 && o.eta == 0.f), "da_sample_loop_ex: the 3D loop has no guidance / stochastic variant");
+    int rc = loop_opts("da_sample_loop_ex", d, opts, &o);
+    if (rc) return rc;
     DA_REQUIRE(inference_ratio >= 1 && s->steps >= 1, "da_sample_loop: bad ratio/steps");
     DA_REQUIRE(d->variant == DA_VARIANT_3D || d->c_in == d->c_out, "da_sample_loop: c_in != c_out");
-    int rc = check_graph(d, g);
-    if (rc) return rc;
+    if ((rc = check_graph(d, g))) return rc;
     Workspace w = carve(d, g, workspace);
     DA_REQUIRE(workspace_bytes >= w.total, "workspace too small: %zu < %zu", workspace_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
-    int total = (s->steps + inference_ratio - 1) / inference_ratio;
-    const int n_iters = (max_iters > 0 && max_iters < total) ? max_iters : total;
+    const int n_iters = loop_iters(s, inference_ratio, max_iters);
+    auto enqueue = [&](hipStream_t on) { return enqueue_loop(d, g, s, mean_type, inference_ratio, n_iters, x_init, traj, x_final, w, on, &o); };
     if (d->prof_on) use_graph = 0;       // event bracketing is not capturable
     // the CALLER is capturing `stream` (e.g. a predict_step wrapped in torch.cuda.graph): the loop's kernels are enqueued on it directly -- they
     // become nodes of the caller's graph -- instead of launching a graph of the library's own from inside a capture
     if (stream_is_capturing(st)) use_graph = 0;
-    if (!use_graph) return enqueue_loop(d, g, s, mean_type, inference_ratio, n_iters, x_init, traj, x_final, w, st, &o);
-
-    LoopKey key;
-    memset(&key, 0, sizeof(key));
-    key.g = *g; key.s = *s; key.mean_type = mean_type; key.ratio = inference_ratio; key.max_iters = n_iters;
-    key.x_init = x_init; key.traj = traj; key.x_final = x_final; key.ws = workspace; key.ws_bytes = workspace_bytes;
-    key.opts = o; key.cfg = cfg();
-    hipGraphExec_t exec = nullptr;
-    for (auto &e : d->loops)
-        if (memcmp(&key, &e.key, sizeof(key)) == 0) exec = e.exec;
-    if (!exec) {
-        if (d->loops.size() >= 8) {                       // small LRU-less cache: drop the oldest (eight: four Batches in flight x two loop lengths)
-            (void)hipGraphExecDestroy(d->loops.front().exec);
-            d->loops.erase(d->loops.begin());
-        }
-        hipGraph_t graph = nullptr;
-        if (!d->cap_stream) DA_CHECK_HIP(hipStreamCreateWithFlags(&d->cap_stream, hipStreamNonBlocking));
-        hipStream_t cs = d->cap_stream;
-        DA_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed));
-        rc = enqueue_loop(d, g, s, mean_type, inference_ratio, n_iters, x_init, traj, x_final, w, cs, &o);
-        hipError_t e = hipStreamEndCapture(cs, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess || !graph) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return 2; }
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) { set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e)); return 2; }
-        d->loops.push_back({key, exec});
-    }
-    DA_CHECK_HIP(hipGraphLaunch(exec, st));
-    return 0;
+    if (!use_graph) return enqueue(st);
+    return launch_loop_graph(d, "da_sample_loop",
+                             loop_key(g, s, mean_type, inference_ratio, n_iters, x_init, traj, x_final, workspace, workspace_bytes, o), enqueue, st);
 }
 
 int da_sample_loop(da_denoiser *d, const da_graph *g, const da_schedule *s, int mean_type, int inference_ratio,
@@ -1077,13 +1158,11 @@ int da_sample_loop_pair_ex(da_denoiser *d, const da_schedule *s, int mean_type, 
     // the samplers of da_sample_loop_ex on both branches: one option set, half a reads opts->noise, half b noise_b (row ranges
     // of one [n_iters, N, c] draw: the poses then equal the one-branch loop's bit for bit)
     da_loop_opts oa, ob;
-    memset(&oa, 0, sizeof(oa));
-    if (opts) { oa.sampler = opts->sampler; oa.eta = opts->eta; oa.cfg = opts->cfg; oa.cfg_w = opts->cfg_w; oa.noise = opts->noise; }
+    int rc = loop_opts("da_sample_loop_pair_ex", d, opts, &oa);
+    if (rc) return rc;
     ob = oa;
     ob.noise = noise_b;
-    DA_REQUIRE(oa.sampler == 0 || oa.sampler == 1, "da_sample_loop_pair_ex: sampler must be 0 (DDIM) or 1 (DDPM)");
-    DA_REQUIRE(!(oa.sampler == 1 || oa.eta > 0.f) || (oa.noise && ob.noise), "da_sample_loop_pair_ex: eta > 0 / DDPM need both noise pointers");
-    DA_REQUIRE(d->variant == DA_VARIANT_2D || (!oa.cfg && oa.sampler == 0 && oa.eta == 0.f), "da_sample_loop_pair_ex: the 3D loop has no guidance / stochastic variant");
+    DA_REQUIRE(!(oa.sampler == 1 || oa.eta > 0.f) || ob.noise, "da_sample_loop_pair_ex: eta > 0 / DDPM need both noise pointers");
     DA_REQUIRE(inference_ratio >= 1 && s->steps >= 1, "da_sample_loop_pair: bad ratio/steps");
     DA_REQUIRE(d->variant == DA_VARIANT_3D || d->c_in == d->c_out, "da_sample_loop_pair: c_in != c_out");
     // hybrid graphs fork the denoiser's side stream (virtual rows) inside every layer: fine when each branch is recorded as a graph of its
@@ -1093,147 +1172,65 @@ int da_sample_loop_pair_ex(da_denoiser *d, const da_schedule *s, int mean_type, 
     DA_REQUIRE((traj_a == nullptr) == (traj_b == nullptr), "da_sample_loop_pair_traj: both trajectory pointers or none");
     DA_REQUIRE(!traj_a || traj_stride >= (size_t)(g_a->n_real + g_b->n_real) * (d->variant == DA_VARIANT_3D ? 7 : d->c_in),
                "da_sample_loop_pair_traj: traj_stride smaller than one iteration of both halves");
-    int rc = check_graph(d, g_a);
-    if (rc) return rc;
-    if ((rc = check_graph(d, g_b))) return rc;
+    if ((rc = check_graph(d, g_a)) || (rc = check_graph(d, g_b))) return rc;
     const Workspace wa = carve(d, g_a, workspace_a), wb = carve(d, g_b, workspace_b);
     DA_REQUIRE(workspace_a_bytes >= wa.total && workspace_b_bytes >= wb.total, "da_sample_loop_pair: workspace too small");
     {
         const char *a0 = (const char *)workspace_a, *b0 = (const char *)workspace_b;
         DA_REQUIRE(a0 + wa.total <= b0 || b0 + wb.total <= a0, "da_sample_loop_pair: the two workspaces overlap");
     }
-    const int total = (s->steps + inference_ratio - 1) / inference_ratio;
-    const int n_iters = (max_iters > 0 && max_iters < total) ? max_iters : total;
-    auto make_key = [&](const da_graph *g, const float *xi, float *xf, void *ws, size_t wsb, float *tr) {
-        LoopKey k;
-        memset(&k, 0, sizeof(k));
-        k.g = *g; k.s = *s; k.mean_type = mean_type; k.ratio = inference_ratio; k.max_iters = n_iters;
-        k.x_init = xi; k.traj = tr; k.x_final = xf; k.ws = ws; k.ws_bytes = wsb; k.traj_stride = tr ? traj_stride : 0;
-        k.cfg = cfg();
-        return k;
+    const int n_iters = loop_iters(s, inference_ratio, max_iters);
+    const LoopKey ka = loop_key(g_a, s, mean_type, inference_ratio, n_iters, x_init_a, traj_a, x_final_a, workspace_a, workspace_a_bytes, oa, traj_stride, noise_stride);
+    const LoopKey kb = loop_key(g_b, s, mean_type, inference_ratio, n_iters, x_init_b, traj_b, x_final_b, workspace_b, workspace_b_bytes, ob, traj_stride, noise_stride);
+    if ((rc = ensure_pair_stream(d))) return rc;
+    hipStream_t us = (hipStream_t)stream, ps = d->pair_stream;
+    auto branch = [&](int br, hipStream_t on) {
+        return br == 0 ? enqueue_loop(d, g_a, s, mean_type, inference_ratio, n_iters, x_init_a, traj_a, x_final_a, wa, on, &oa, traj_stride, noise_stride)
+                       : enqueue_loop(d, g_b, s, mean_type, inference_ratio, n_iters, x_init_b, traj_b, x_final_b, wb, on, &ob, traj_stride, noise_stride);
     };
-    LoopKey ka = make_key(g_a, x_init_a, x_final_a, workspace_a, workspace_a_bytes, traj_a);
-    LoopKey kb = make_key(g_b, x_init_b, x_final_b, workspace_b, workspace_b_bytes, traj_b);
-    ka.opts = oa; kb.opts = ob;
-    ka.noise_stride = oa.noise ? noise_stride : 0; kb.noise_stride = ob.noise ? noise_stride : 0;
+    // both branches under ONE capture of `on`: branch A on it, branch B on the pair stream between a fork and a join (two parallel branches of
+    // that capture's graph); the join also runs when a branch fails, so the capture is never left forked
+    auto both = [&](hipStream_t on, int delay_us) -> int {
+        StreamJoin join;
+        int r = fork_pair_stream(d, on, join);
+        if (r) return r;
+        if (delay_us > 0) k_pair_delay<<<1, 64, 0, ps>>>((unsigned long long)delay_us * 100ull);
+        if ((r = branch(0, on)) || (r = branch(1, ps))) return r;
+        DA_CHECK_HIP(join.join());
+        return 0;
+    };
+    // the caller is capturing `stream`: both branches go straight into the caller's capture -- no graph of the library's own is launched
+    if (stream_is_capturing(us)) return both(us, 0);
     // DA_PAIR_SPLIT (default 1): the two branches as TWO graphs, launched on the caller's stream and on the library's pair stream between a
     // fork and a join event, instead of two parallel branches of one graph.  Measured (tools/multi_branch_probe.py, round 5): two independently
     // launched one-branch graphs of 32 puzzles ran a 64-puzzle step in 0.6734 ms where the one-graph pair loop needed 0.7002 on the same box --
     // the runtime does not run the two branches of one graph as independently as it runs two graphs on two streams.
-    const int split_mode = cfg().pair_split;
-    if (stream_is_capturing((hipStream_t)stream)) {
-        // the caller is capturing `stream`: both branches go straight into the caller's capture -- branch A on `stream`, branch B on the library's
-        // pair stream between a fork and a join event (two parallel branches of the CALLER's graph) -- no graph of the library's own is launched
-        hipStream_t us = (hipStream_t)stream;
-        if (!d->pair_stream) {
-            DA_CHECK_HIP(hipStreamCreateWithFlags(&d->pair_stream, hipStreamNonBlocking));
-            DA_CHECK_HIP(hipEventCreateWithFlags(&d->ev_pair_fork, hipEventDisableTiming));
-            DA_CHECK_HIP(hipEventCreateWithFlags(&d->ev_pair_join, hipEventDisableTiming));
-        }
-        hipStream_t ps = d->pair_stream;
-        DA_CHECK_HIP(hipEventRecord(d->ev_pair_fork, us));
-        DA_CHECK_HIP(hipStreamWaitEvent(ps, d->ev_pair_fork, 0));
-        const int rca = enqueue_loop(d, g_a, s, mean_type, inference_ratio, n_iters, x_init_a, traj_a, x_final_a, wa, us, &oa, traj_stride, noise_stride);
-        const int rcb = enqueue_loop(d, g_b, s, mean_type, inference_ratio, n_iters, x_init_b, traj_b, x_final_b, wb, ps, &ob, traj_stride, noise_stride);
-        DA_CHECK_HIP(hipEventRecord(d->ev_pair_join, ps));           // (joined even when a branch failed: the capture must not be left forked)
-        DA_CHECK_HIP(hipStreamWaitEvent(us, d->ev_pair_join, 0));
-        return rca ? rca : rcb;
-    }
-    hipGraphExec_t exec = nullptr, exec_b = nullptr;
-    for (auto &e : d->pair_loops)
-        if (memcmp(&ka, &e.a, sizeof(ka)) == 0 && memcmp(&kb, &e.b, sizeof(kb)) == 0 && (e.exec_b != nullptr) == (split_mode != 0)) { exec = e.exec; exec_b = e.exec_b; }
-    if (!exec && split_mode) {
-        if (d->pair_loops.size() >= 4) {
-            (void)hipGraphExecDestroy(d->pair_loops.front().exec);
-            if (d->pair_loops.front().exec_b) (void)hipGraphExecDestroy(d->pair_loops.front().exec_b);
-            d->pair_loops.erase(d->pair_loops.begin());
-        }
-        if (!d->cap_stream) DA_CHECK_HIP(hipStreamCreateWithFlags(&d->cap_stream, hipStreamNonBlocking));
-        if (!d->pair_stream) {
-            // DA_PAIR_PRIO (experiment, default 0): 1 = the pair stream at the device's highest priority, -1 = at its lowest -- a standing
-            // asymmetry between the branches (one takes free slots first, the other fills its tails) instead of two equals in lockstep
-            const int prio = DA_XENV("DA_PAIR_PRIO", 0);
-            if (prio) {
-                int lo = 0, hi = 0;                                                     // lo = numerically greatest = lowest priority
-                DA_CHECK_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-                DA_CHECK_HIP(hipStreamCreateWithPriority(&d->pair_stream, hipStreamNonBlocking, prio > 0 ? hi : lo));
-            } else
-                DA_CHECK_HIP(hipStreamCreateWithFlags(&d->pair_stream, hipStreamNonBlocking));
-            DA_CHECK_HIP(hipEventCreateWithFlags(&d->ev_pair_fork, hipEventDisableTiming));
-            DA_CHECK_HIP(hipEventCreateWithFlags(&d->ev_pair_join, hipEventDisableTiming));
-        }
-        hipGraphExec_t ex2[2] = {nullptr, nullptr};
-        for (int br = 0; br < 2; ++br) {
-            hipStream_t cs = d->cap_stream;
-            hipGraph_t graph = nullptr;
-            DA_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed));
-            const int rcx = br == 0 ? enqueue_loop(d, g_a, s, mean_type, inference_ratio, n_iters, x_init_a, traj_a, x_final_a, wa, cs, &oa, traj_stride, noise_stride)
-                                    : enqueue_loop(d, g_b, s, mean_type, inference_ratio, n_iters, x_init_b, traj_b, x_final_b, wb, cs, &ob, traj_stride, noise_stride);
-            const hipError_t e2 = hipStreamEndCapture(cs, &graph);
-            hipError_t e3 = hipSuccess;
-            if (!rcx && e2 == hipSuccess && graph) e3 = hipGraphInstantiate(&ex2[br], graph, nullptr, nullptr, 0);
-            if (graph) (void)hipGraphDestroy(graph);
-            if (rcx || e2 != hipSuccess || e3 != hipSuccess || !ex2[br]) {
-                if (ex2[0]) (void)hipGraphExecDestroy(ex2[0]);
-                if (rcx) return rcx;
-                set_error("da_sample_loop_pair: capture of branch %d failed: %s", br, hipGetErrorString(e2 != hipSuccess ? e2 : e3));
-                return 2;
+    const bool split = cfg().pair_split != 0;
+    const da_denoiser::LoopEntry *hit = cache_find(d->pair_loops, ka, kb, split);
+    hipGraphExec_t exec = hit ? hit->exec : nullptr, exec_b = hit ? hit->exec_b : nullptr;
+    if (!hit) {
+        if (split) {
+            if ((rc = record_graph(d, "da_sample_loop_pair, branch a", [&](hipStream_t cs) { return branch(0, cs); }, &exec))) return rc;
+            if ((rc = record_graph(d, "da_sample_loop_pair, branch b", [&](hipStream_t cs) { return branch(1, cs); }, &exec_b))) {
+                (void)hipGraphExecDestroy(exec);
+                return rc;
             }
-        }
-        exec = ex2[0]; exec_b = ex2[1];
-        d->pair_loops.push_back({ka, kb, exec, exec_b});
-    }
-    if (exec && exec_b) {
-        hipStream_t us = (hipStream_t)stream, ps = d->pair_stream;
-        DA_CHECK_HIP(hipEventRecord(d->ev_pair_fork, us));
-        DA_CHECK_HIP(hipStreamWaitEvent(ps, d->ev_pair_fork, 0));
-        DA_CHECK_HIP(hipGraphLaunch(exec, us));
-        DA_CHECK_HIP(hipGraphLaunch(exec_b, ps));
-        DA_CHECK_HIP(hipEventRecord(d->ev_pair_join, ps));
-        DA_CHECK_HIP(hipStreamWaitEvent(us, d->ev_pair_join, 0));
-        return 0;
-    }
-    if (!exec) {
-        if (d->pair_loops.size() >= 4) {
-            (void)hipGraphExecDestroy(d->pair_loops.front().exec);
-            if (d->pair_loops.front().exec_b) (void)hipGraphExecDestroy(d->pair_loops.front().exec_b);
-            d->pair_loops.erase(d->pair_loops.begin());
-        }
-        if (!d->cap_stream) DA_CHECK_HIP(hipStreamCreateWithFlags(&d->cap_stream, hipStreamNonBlocking));
-        if (!d->pair_stream) {
-            DA_CHECK_HIP(hipStreamCreateWithFlags(&d->pair_stream, hipStreamNonBlocking));
-            DA_CHECK_HIP(hipEventCreateWithFlags(&d->ev_pair_fork, hipEventDisableTiming));
-            DA_CHECK_HIP(hipEventCreateWithFlags(&d->ev_pair_join, hipEventDisableTiming));
-        }
-        hipStream_t cs = d->cap_stream, ps = d->pair_stream;
-        hipGraph_t graph = nullptr;
-        DA_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed));
-        hipError_t e = hipEventRecord(d->ev_pair_fork, cs);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ps, d->ev_pair_fork, 0);                 // ps joins the capture
-        int rca = 0, rcb = 0;
-        if (e == hipSuccess) {
+        } else {
             // experiment switch (DA_PAIR_DELAY_US, default 0): branch B starts this many microseconds after branch A, so that the two
             // branches run out of phase for the whole loop (one branch's attention beside the other's projections)
-            const int delay_us = DA_XENV("DA_PAIR_DELAY_US", 0);
-            if (delay_us > 0) k_pair_delay<<<1, 64, 0, ps>>>((unsigned long long)delay_us * 100ull);
-            rca = enqueue_loop(d, g_a, s, mean_type, inference_ratio, n_iters, x_init_a, traj_a, x_final_a, wa, cs, &oa, traj_stride, noise_stride);
-            rcb = enqueue_loop(d, g_b, s, mean_type, inference_ratio, n_iters, x_init_b, traj_b, x_final_b, wb, ps, &ob, traj_stride, noise_stride);
-            e = hipEventRecord(d->ev_pair_join, ps);
-            if (e == hipSuccess) e = hipStreamWaitEvent(cs, d->ev_pair_join, 0);
+            if ((rc = record_graph(d, "da_sample_loop_pair", [&](hipStream_t cs) { return both(cs, DA_XENV("DA_PAIR_DELAY_US", 0)); }, &exec))) return rc;
         }
-        const hipError_t e2 = hipStreamEndCapture(cs, &graph);
-        if (rca || rcb) { if (graph) (void)hipGraphDestroy(graph); return rca ? rca : rcb; }
-        if (e != hipSuccess || e2 != hipSuccess || !graph) {
-            if (graph) (void)hipGraphDestroy(graph);
-            set_error("da_sample_loop_pair: capture failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-            return 2;
-        }
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) { set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e)); return 2; }
-        d->pair_loops.push_back({ka, kb, exec, nullptr});
+        cache_insert(d->pair_loops, 4, {ka, kb, exec, exec_b});
     }
-    DA_CHECK_HIP(hipGraphLaunch(exec, (hipStream_t)stream));
+    if (!exec_b) {
+        DA_CHECK_HIP(hipGraphLaunch(exec, us));
+        return 0;
+    }
+    StreamJoin join;
+    if ((rc = fork_pair_stream(d, us, join))) return rc;
+    DA_CHECK_HIP(hipGraphLaunch(exec, us));
+    DA_CHECK_HIP(hipGraphLaunch(exec_b, ps));
+    DA_CHECK_HIP(join.join());
     return 0;
 }
 
@@ -1312,40 +1309,16 @@ int da_sample_loop_idx(da_denoiser *d, const da_graph *g, const da_schedule *s, 
     Workspace w = carve(d, g, workspace);
     DA_REQUIRE(workspace_bytes >= w.total, "workspace too small: %zu < %zu", workspace_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
-    const int total = (s->steps + inference_ratio - 1) / inference_ratio;
-    const int n_iters = (max_iters > 0 && max_iters < total) ? max_iters : total;
+    const int n_iters = loop_iters(s, inference_ratio, max_iters);
+    auto enqueue = [&](hipStream_t on) { return enqueue_loop_idx(d, g, s, inference_ratio, n_iters, idx_init, traj, idx_final, w, on, o); };
     // the capture rules of da_sample_loop_ex: eager while profiling, straight into a capture the caller has open
     if (d->prof_on || stream_is_capturing(st)) use_graph = 0;
-    if (!use_graph) return enqueue_loop_idx(d, g, s, inference_ratio, n_iters, idx_init, traj, idx_final, w, st, o);
-
-    LoopKey key;
-    memset(&key, 0, sizeof(key));
-    key.g = *g; key.s = *s; key.mean_type = -1 /* the discrete loop */; key.ratio = inference_ratio; key.max_iters = n_iters;
-    key.x_init = (const float *)idx_init; key.traj = (float *)traj; key.x_final = (float *)idx_final; key.ws = workspace; key.ws_bytes = workspace_bytes;
-    key.opts.cfg = o.cfg; key.opts.cfg_w = o.cfg_w; key.opts.noise = o.noise; key.seed = o.seed; key.cfg = cfg();
-    hipGraphExec_t exec = nullptr;
-    for (auto &e : d->loops)
-        if (memcmp(&key, &e.key, sizeof(key)) == 0) exec = e.exec;
-    if (!exec) {
-        if (d->loops.size() >= 8) {
-            (void)hipGraphExecDestroy(d->loops.front().exec);
-            d->loops.erase(d->loops.begin());
-        }
-        hipGraph_t graph = nullptr;
-        if (!d->cap_stream) DA_CHECK_HIP(hipStreamCreateWithFlags(&d->cap_stream, hipStreamNonBlocking));
-        hipStream_t cs = d->cap_stream;
-        DA_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed));
-        rc = enqueue_loop_idx(d, g, s, inference_ratio, n_iters, idx_init, traj, idx_final, w, cs, o);
-        hipError_t e = hipStreamEndCapture(cs, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess || !graph) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(e)); return 2; }
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) { set_error("hipGraphInstantiate failed: %s", hipGetErrorString(e)); return 2; }
-        d->loops.push_back({key, exec});
-    }
-    DA_CHECK_HIP(hipGraphLaunch(exec, st));
-    return 0;
+    if (!use_graph) return enqueue(st);
+    da_loop_opts ko;                    // the key's share of the discrete options (mean_type -1 marks the discrete loop)
+    memset(&ko, 0, sizeof(ko));
+    ko.cfg = o.cfg; ko.cfg_w = o.cfg_w; ko.noise = o.noise;
+    return launch_loop_graph(d, "da_sample_loop_idx",
+                             loop_key(g, s, -1, inference_ratio, n_iters, idx_init, traj, idx_final, workspace, workspace_bytes, ko, 0, 0, o.seed), enqueue, st);
 }
 
 size_t da_attn_dense_scratch_bytes(int prec, const da_graph *g, int heads, int C) {

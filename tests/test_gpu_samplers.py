@@ -198,3 +198,116 @@ def test_sampling_loops_inside_a_callers_graph_capture(dev, monkeypatch, pair):
     g.replay()                                                      # (a second replay: the captured loop is self-contained)
     torch.cuda.synchronize()
     assert torch.equal(xf, ref)
+
+
+def test_one_branch_graph_cache_evicts_and_records_again(dev):
+    """The one-branch loop cache holds 8 graphs, oldest first.  Ten loop lengths (ten keys: the engine's pose buffers are per length)
+    push lengths 1 and 2 out; running those again records them again, length 10 is still cached and replayed.  Every captured
+    result equals the eager loop of the same length bit for bit (the eager result's buffer is poisoned before the captured call
+    writes it, so a replay that did nothing cannot pass)."""
+    from diffassemble_amd import _lib
+    spec, case, eng, plan, sch_cpu, sch = _setup(dev)
+    x0, feats = case["x"].to(dev), case["feats"].to(dev)
+    kw = dict(ratio=1, mean_type=_lib.MEAN_START_X)
+
+    def check(k):
+        _, buf = eng.sample_loop(plan, sch, x0, feats, max_iters=k, use_graph=False, **kw)
+        ref = buf.clone()
+        buf.fill_(float("nan"))
+        _, xf = eng.sample_loop(plan, sch, x0, feats, max_iters=k, use_graph=True, **kw)
+        assert torch.isfinite(ref).all() and torch.equal(xf, ref), k
+
+    for k in range(1, 11):
+        check(k)
+    for k in (1, 2, 10):        # evicted, evicted, still cached
+        check(k)
+
+
+def _pair_cache_batch(eng, dev):
+    """G = 2 puzzles of 36 pieces when the engine takes that Batch as a two-branch loop, else the 4 x 144 of the capture test."""
+    from oracle import weights as W
+    for n, G in ((36, 2), (144, 4)):
+        ei, batch = W.collate([W.dense_edge_index(n, True) for _ in range(G)], [n] * G)
+        plan = eng.plan(ei.to(dev), batch.to(dev))
+        if eng._two_branch(plan, False, True):
+            return plan, n * G
+    raise AssertionError("no Batch of this test takes the two-branch loop")
+
+
+def test_pair_graph_cache_evicts_and_records_again(dev, monkeypatch):
+    """The pair cache holds 4 entries.  Five loop lengths push length 1 out, which is then recorded again; every pair loop equals the
+    one-branch loop of the same length bit for bit.  Runs in the form da_config.pair_split selects (two graphs by default; the
+    subprocess test below runs it as one graph)."""
+    from diffassemble_amd import DenoiserEngine, Schedule, _lib
+    from oracle import weights as W
+    sd = W.make_denoiser_state(50, 4, 4, seed=11)
+    eng = DenoiserEngine(sd, precision="bf16", device=dev)
+    monkeypatch.setenv("DA_TWO_BRANCH", "1")
+    monkeypatch.setattr(eng, "two_branch_min_graphs", 2, raising=False)
+    plan, N = _pair_cache_batch(eng, dev)
+    gen = torch.Generator().manual_seed(3)
+    x0 = torch.randn((N, 4), generator=gen).to(dev)
+    feats = torch.randn((N, 1088), generator=gen).to(dev)
+    sch = Schedule(ODF.make_schedule(50), dev)
+    kw = dict(ratio=5, mean_type=_lib.MEAN_START_X, keep_trajectory=False, use_graph=True)
+    for k in (1, 2, 3, 4, 5, 1):
+        monkeypatch.setenv("DA_TWO_BRANCH", "0")
+        assert not eng._two_branch(plan, False, True)
+        _, one = eng.sample_loop(plan, sch, x0, feats, max_iters=k, **kw)
+        ref = one.clone()
+        monkeypatch.setenv("DA_TWO_BRANCH", "1")
+        assert eng._two_branch(plan, False, True)
+        _, xf = eng.sample_loop(plan, sch, x0, feats, max_iters=k, **kw)
+        assert torch.isfinite(ref).all() and torch.equal(xf, ref), k
+        xf.fill_(float("nan"))          # (the pair loop's own buffer: the next length has to write it)
+
+
+def test_pair_graph_cache_as_one_graph_subprocess():
+    """DA_PAIR_SPLIT=0: the same eviction test with both branches in ONE graph (a process of its own: the switch is read when the
+    library's configuration is first used)."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.abspath(__file__), "-k", "test_pair_graph_cache_evicts_and_records_again"],
+                       env=dict(os.environ, DA_PAIR_SPLIT="0"), capture_output=True, text=True, cwd=root)
+    assert r.returncode == 0 and "1 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+def test_refused_recording_leaves_the_denoiser_usable_subprocess():
+    """DA_DISABLE_MFMA=1: the guided loop's unconditional pass does not exist, so the library's argument check refuses the loop in
+    the MIDDLE of recording it (an error code, no kernel involved).  The capture must be ended all the same: the next loop on the
+    same engine records on the same capture stream, runs, and equals its eager form bit for bit."""
+    import os
+    import subprocess
+    import sys
+    code = r'''
+import sys, torch
+sys.path.insert(0, "tests/golden")
+import cases as C
+from oracle import diffusion as ODF
+from diffassemble_amd import DenoiserEngine, Schedule, _lib
+dev = torch.device("cuda:0")
+case = C.build_case(C.by_name("k36_loop_sharp"))
+eng = DenoiserEngine(case["sd"], precision="fp32", device=dev)
+plan = eng.plan(case["edge_index"], case["batch"])
+sch = Schedule(ODF.make_schedule(50), dev)
+x0, feats = case["x"].to(dev), case["feats"].to(dev)
+kw = dict(ratio=1, mean_type=_lib.MEAN_START_X)
+try:
+    eng.sample_loop(plan, sch, x0, feats, cfg_w=0.5, use_graph=True, **kw)
+except _lib.DaError as e:
+    assert "unconditional pass" in str(e), str(e)
+else:
+    raise AssertionError("the guided loop was not refused")
+_, buf = eng.sample_loop(plan, sch, x0, feats, max_iters=5, use_graph=False, **kw)
+ref = buf.clone()
+buf.fill_(float("nan"))
+_, xf = eng.sample_loop(plan, sch, x0, feats, max_iters=5, use_graph=True, **kw)
+torch.cuda.synchronize()
+assert torch.isfinite(ref).all() and torch.equal(xf, ref)
+print("refused-then-recorded OK")
+'''
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, DA_DISABLE_MFMA="1"), capture_output=True, text=True, cwd=root)
+    assert r.returncode == 0 and "refused-then-recorded OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
