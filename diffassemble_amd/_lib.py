@@ -23,6 +23,8 @@ ACT_NONE, ACT_GELU, ACT_LEAKY02 = 0, 1, 2
 CONV_Q_PRESCALED, CONV_FOLDED_V32 = 1, 2
 TRAIN_MMA_FP32, TRAIN_MMA_BF16 = 0, 1
 TRAIN_BWD_ALL, TRAIN_BWD_EARLY, TRAIN_BWD_LATE = 0, 1, 2
+D3PM_DRAW_SAMPLING, D3PM_DRAW_TRAINING = 0, 1
+D3PM_LOSS = {"vb": 0, "cross_entropy": 1, "hybrid": 2}
 DBG_COUNTERS = ("opt_gen_workgroups", "dense_fast_exits", "dual_gen_slabs", "opt_masked_gen_workgroups")          # fallback events (indices 0 .. 3)
 DBG_LAUNCH_COUNTERS = {"resident_launches": 4, "virtual_rows_in_launch": 5}          # which kernel took a layer (DA_DBG_RES_LAUNCHES, DA_DBG_VIRT_IN_LAUNCH)
 PROF_CLASSES = ("embed", "linear_mlp", "linear_qkvs", "attn_hidden", "attn_last", "head", "update", "conv_fused")
@@ -196,6 +198,12 @@ PROTOTYPES = {
     "da_denoiser_forward_idx": (C.c_int, [_fp, C.POINTER(DaGraph), _fp, _fp, C.c_int64, _fp, _fp, C.c_int, _fp, C.c_size_t, _fp]),
     "da_d3pm_step": (C.c_int, [C.POINTER(DaSchedule), C.c_int, C.c_int, _fp, _fp, _fp, C.c_int64, C.c_int, _fp, _fp, C.c_int, _fp, _fp, _fp]),
     "da_d3pm_noise": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "da_d3pm_noise_ex": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "da_d3pm_q_sample": (C.c_int, [C.POINTER(DaSchedule), C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp]),
+    "da_d3pm_loss": (C.c_int, [C.POINTER(DaSchedule), C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "da_train_forward_idx": (C.c_int, [C.POINTER(DaWeights), C.POINTER(DaGraph), _fp, _fp, _fp, _fp, _fp, C.c_size_t, C.c_int, _fp]),
+    "da_train_backward_idx": (C.c_int, [C.POINTER(DaWeights), C.POINTER(DaWeights), C.POINTER(DaGraph), _fp, _fp, _fp, _fp,
+                                        _fp, C.c_size_t, C.c_int, C.c_int, _fp]),
     "da_sample_loop_idx": (C.c_int, [_fp, C.POINTER(DaGraph), C.POINTER(DaSchedule), C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t,
                                      C.c_int, C.POINTER(DaD3pmOpts), _fp]),
     "da_profile_enable": (C.c_int, [_fp, C.c_int]),

@@ -40,25 +40,11 @@ __global__ __launch_bounds__(256) void k_embed_idx_time(int n, int K, int F, int
 }
 
 // ------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al., SC'11).  One uniform per flat element e = r K + k: key = the two halves of seed[0], counter =
-// (e + seed[1] as 64 bits, iteration, a constant); the first output word gives u = ((bits >> 8) + 1) 2^-24 in (0, 1].
-__device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t ctr, uint32_t iteration) {
-    uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = iteration, c3 = 0xD3B07384u;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return (float)((c0 >> 8) + 1u) * 5.9604644775390625e-8f;
-}
-
-__global__ __launch_bounds__(256) void k_d3pm_noise(const uint64_t *__restrict__ seed, uint32_t iteration, size_t total,
+// (philox_uniform: da_internal.h, shared with the training-side noising of da_d3pm_train.hip)
+__global__ __launch_bounds__(256) void k_d3pm_noise(const uint64_t *__restrict__ seed, uint32_t iteration, uint32_t domain, size_t total,
                                                     float *__restrict__ u) {
     const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < total) u[e] = philox_uniform(seed[0], (uint64_t)e + seed[1], iteration);
+    if (e < total) u[e] = philox_uniform(seed[0], (uint64_t)e + seed[1], iteration, domain);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -242,10 +228,15 @@ int da_d3pm_step(const da_schedule *s, int n, int K, const int32_t *x_t, const f
 }
 
 int da_d3pm_noise(const uint64_t *seed, int iteration, int n, int K, float *u, void *stream) {
+    return da_d3pm_noise_ex(seed, iteration, n, K, DA_D3PM_DRAW_SAMPLING, u, stream);
+}
+
+int da_d3pm_noise_ex(const uint64_t *seed, int iteration, int n, int K, int domain, float *u, void *stream) {
     DA_REQUIRE(seed && u && n >= 0 && K >= 1, "da_d3pm_noise: bad argument");
+    DA_REQUIRE(domain == DA_D3PM_DRAW_SAMPLING || domain == DA_D3PM_DRAW_TRAINING, "da_d3pm_noise: unknown draw domain %d", domain);
     const size_t total = (size_t)n * K;
     if (!total) return 0;
-    k_d3pm_noise<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(seed, (uint32_t)iteration, total, u);
+    k_d3pm_noise<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(seed, (uint32_t)iteration, d3pm_domain_word(domain), total, u);
     DA_LAUNCH_CHECK();
     return 0;
 }

@@ -257,6 +257,26 @@ int launch_embed_idx_time(int prec, int n, int K, int F, int D, const int32_t *i
 struct D3pmRows {
     const void *hh = nullptr, *pz = nullptr, *pre = nullptr;
 };
+// Philox4x32-10 (Salmon et al., SC'11).  One uniform per flat element e = r K + k: key = the two halves of seed[0], counter =
+// (e + seed[1] as 64 bits, iteration, a constant); the first output word gives u = ((bits >> 8) + 1) 2^-24 in (0, 1].  The constant
+// names the draw's DOMAIN: the reverse step's Gumbel uniforms (the default) and the training-side noising of q_sample
+// (da_d3pm_train.hip) use different words, so one seed never gives the two the same stream.
+constexpr uint32_t D3PM_WORD_SAMPLING = 0xD3B07384u, D3PM_WORD_TRAINING = 0x51ED270Bu;
+inline uint32_t d3pm_domain_word(int domain) { return domain == DA_D3PM_DRAW_TRAINING ? D3PM_WORD_TRAINING : D3PM_WORD_SAMPLING; }
+__device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t ctr, uint32_t iteration, uint32_t word = D3PM_WORD_SAMPLING) {
+    uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = iteration, c3 = word;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return (float)((c0 >> 8) + 1u) * 5.9604644775390625e-8f;
+}
+// da_d3pm_train.hip: pos_mlp.weight.grad[idx[r]] += dcomb[r, F : F + 32], one owner per table row, fixed order
+int launch_embed_idx_grad(int n, int K, int D, int F, const int32_t *idx, const float *dcomb, float *grad, hipStream_t st);
 // logits from the conditional rows (and the unconditional ones under guidance) through w2 / b2, or given (logits_in: rows_c may be
 // NULL); logits_out nullable; step == NULL: logits only
 int launch_d3pm_tail(int prec, int n, int K, int H, const D3pmRows *rows_c, const D3pmRows *rows_u, float cfg_w, const float *w2,

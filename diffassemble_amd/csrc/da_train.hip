@@ -895,6 +895,7 @@ struct Dims {
     bool gelu_between;
     bool v3d;                  // DA_VARIANT_3D (efficient_gat_3d.py): LeakyReLU mlp, two pose heads behind one 512-wide hidden product
     int hh;                    // width of the head's hidden layer: 32 (final_mlp.0), 3D: 512 (mlp_t.0 | mlp_r.0)
+    bool disc;                 // DA_VARIANT_DISCRETE (efficient_gat_discrete.py): embedding lookup where the pose MLP was, K-wide logits head (c_out = K)
     bool gcn;                  // DA_ARCH_GCN (backbones/gcn.py): two GCNConv, aggregation by da_gcn.hip, no attention
     bool dense;                // complete graphs: grouped-GEMM attention (da_train_dense.hip)
     bool hybrid;               // hybrid graphs: masked grouped GEMMs + CSR remainder (da_train_dense.hip)
@@ -909,8 +910,14 @@ struct Dims {
 static int dims_of(const da_weights *w, const da_graph *g, Dims &d, int mma = DA_TRAIN_MMA_FP32) {
     d.bfc = mma == DA_TRAIN_MMA_BF16;
     DA_REQUIRE(w && g, "training: null argument");
-    DA_REQUIRE(w->variant == DA_VARIANT_2D || w->variant == DA_VARIANT_3D, "training: unknown variant %d", w->variant);
+    DA_REQUIRE(w->variant == DA_VARIANT_2D || w->variant == DA_VARIANT_3D || w->variant == DA_VARIANT_DISCRETE, "training: unknown variant %d", w->variant);
     d.v3d = w->variant == DA_VARIANT_3D;
+    d.disc = w->variant == DA_VARIANT_DISCRETE;
+    if (d.disc) {
+        DA_REQUIRE(w->arch == DA_ARCH_TRANSFORMER, "training (discrete variant): the transformer architecture only, as in inference");
+        DA_REQUIRE(w->c_out >= 2 && w->c_out <= 1024, "training (discrete variant): K = c_out = %d outside [2, 1024]", w->c_out);
+        DA_REQUIRE(w->c_in == 1 && w->pos_w1, "training (discrete variant): c_in must be 1 and pos_w1 = pos_mlp.weight [K, 32]");
+    }
     d.hh = d.v3d ? 512 : 32;
     DA_REQUIRE(!d.v3d || w->c_in == 7, "training (3D): c_in must be 7 (quaternion wxyz | translation), not %d", w->c_in);
     DA_REQUIRE(w->c_in >= 1 && w->c_in <= 8, "training: c_in %d outside 1 .. 8", w->c_in);
@@ -1077,7 +1084,7 @@ static int weight_prep(const da_weights *w, const Dims &d, TrainWs &ws, hipStrea
     add(w->head_w0, ws.wt_head0, d.hh, d.D, 0);
     add(w->mlp_w1, ws.wt_mlp1, d.D, d.hid, 0);
     add(w->mlp_w0, ws.wt_mlp0, d.hid, d.D, 0);
-    add(w->pos_w1, ws.wt_pos1, 32, 16, 0);
+    if (!d.disc) add(w->pos_w1, ws.wt_pos1, 32, 16, 0);        // (discrete: pos_w1 is the [K, 32] embedding table, no product)
     for (int l = 0; l < d.L && d.gcn; ++l) add(w->conv_wq[l], ws.wt_conv[l], d.hc[l], d.din[l], 0);       // GCNConv lin.weight^T
     for (int l = 0; l < d.L && !d.gcn; ++l) {
         add(w->conv_wq[l], ws.wt_conv[l], 4 * d.hc[l], d.din[l], d.q16 ? 1 : 0);
@@ -1248,13 +1255,20 @@ int da_train_forward(const da_weights *w, const da_graph *g, const float *x, con
     return da_train_forward_ex(w, g, x, t, feats, out, workspace, workspace_bytes, DA_TRAIN_MMA_FP32, stream);
 }
 
-int da_train_forward_ex(const da_weights *w, const da_graph *g, const float *x, const int64_t *t, const float *feats,
-                        float *out, void *workspace, size_t workspace_bytes, int mma_precision, void *stream) {
+// One implementation behind the float-pose and the index entries.  x: float poses [n_real, c_in] (2D, 3D) or idx: position indices
+// [n_real] (discrete) -- exactly one of the two
+static int train_backward_impl(const da_weights *w, const da_weights *grads, const da_graph *g, const float *x, const int32_t *idx,
+                               const int64_t *t, const float *d_out, float *d_feats, void *workspace, size_t workspace_bytes,
+                               int mma_precision, int stage, void *stream);
+static int train_forward_impl(const da_weights *w, const da_graph *g, const float *x, const int32_t *idx, const int64_t *t, const float *feats,
+                              float *out, void *workspace, size_t workspace_bytes, int mma_precision, void *stream) {
     Dims d;
     int rc;
     DA_REQUIRE(mma_precision == DA_TRAIN_MMA_FP32 || mma_precision == DA_TRAIN_MMA_BF16, "da_train_forward: unknown mma_precision %d", mma_precision);
     if ((rc = dims_of(w, g, d, mma_precision))) return rc;
-    DA_REQUIRE(x && t && feats && out && workspace, "da_train_forward: null argument");
+    DA_REQUIRE(idx || !d.disc, "da_train_forward: a discrete denoiser takes position indices (da_train_forward_idx)");
+    DA_REQUIRE(!idx || d.disc, "da_train_forward_idx: not a discrete denoiser (da_train_forward_ex takes poses)");
+    DA_REQUIRE((x || idx) && t && feats && out && workspace, "da_train_forward: null argument");
     if ((rc = check_fused(w, d, "da_train_forward"))) return rc;
     TrainWs ws = carve_train(d, workspace);
     DA_REQUIRE(workspace_bytes >= ws.total, "training workspace too small: %zu < %zu", workspace_bytes, ws.total);
@@ -1276,6 +1290,9 @@ int da_train_forward_ex(const da_weights *w, const da_graph *g, const float *x, 
     hipEvent_t ev_images = sd ? sd->done[0] : nullptr;       // (done[] belongs to the backward; idle during a forward)
     if (sd) DA_CHECK_HIP(hipEventRecord(ev_images, sd->s));
     if ((rc = launch_set_feats(P, nr, d.F, D, feats, ws.comb_in, st))) return rc;
+    if (d.disc) {          // the embed is a gather: pos_mlp.weight[idx] | time_emb[t] (efficient_gat_discrete.py:81-86)
+        if ((rc = launch_embed_idx_time(P, nr, d.c_out, d.F, D, idx, t, 0, w->steps, w->time_emb, w->pos_w1, ws.comb_in, st))) return rc;
+    } else
     if ((rc = launch_embed_pos_time(P, nr, d.c_in, d.F, D, x, t, 0, w->steps, w->time_emb, w->pos_w0, w->pos_b0, w->pos_w1,
                                     w->pos_b1, ws.comb_in, st))) return rc;
     // mlp: Linear GELU Linear (efficient_gat.py:135); 3D: Linear LeakyReLU(0.2) Linear LeakyReLU(0.2) (efficient_gat_3d.py:136-141)
@@ -1293,6 +1310,11 @@ int da_train_forward_ex(const da_weights *w, const da_graph *g, const float *x, 
         int r;
         if ((r = linear_fw(d, ws, nr, D, d.hh, zin, D, w->head_w0, w->head_b0, ws.f1pre, d.hh, st, ws.f1))) return r;
         if (d.v3d) return launch_head3d(P, nr, ws.f1, w->head_w1, w->head_b1, w->head_r_w1, w->head_r_b1, out, ws.pre6, st);
+        if (d.disc) {      // Linear(32, K): the logits half of the sampling step's tail kernel (fp32 in both modes, row k of final_mlp.2 in registers)
+            D3pmRows rows;
+            rows.hh = ws.f1;
+            return launch_d3pm_tail(P, nr, d.c_out, d.H, &rows, nullptr, 0.f, w->head_w1, w->head_b1, nullptr, out, nullptr, st);
+        }
         return launch_head2d(P, nr, d.c_out, ws.f1, w->head_w1, w->head_b1, out, st);
     };
     if (d.gcn) {
@@ -1363,6 +1385,32 @@ int da_train_forward_ex(const da_weights *w, const da_graph *g, const float *x, 
     return head_fw(z);
 }
 
+int da_train_forward_ex(const da_weights *w, const da_graph *g, const float *x, const int64_t *t, const float *feats,
+                        float *out, void *workspace, size_t workspace_bytes, int mma_precision, void *stream) {
+    DA_REQUIRE(x, "da_train_forward: null argument");
+    return train_forward_impl(w, g, x, nullptr, t, feats, out, workspace, workspace_bytes, mma_precision, stream);
+}
+
+int da_train_forward_idx(const da_weights *w, const da_graph *g, const int32_t *idx, const int64_t *t, const float *feats,
+                         float *logits, void *workspace, size_t workspace_bytes, int mma_precision, void *stream) {
+    DA_REQUIRE(idx, "da_train_forward_idx: null argument");
+    return train_forward_impl(w, g, nullptr, idx, t, feats, logits, workspace, workspace_bytes, mma_precision, stream);
+}
+
+int da_train_backward_stage(const da_weights *w, const da_weights *grads, const da_graph *g, const float *x,
+                            const int64_t *t, const float *d_out, float *d_feats, void *workspace, size_t workspace_bytes,
+                            int mma_precision, int stage, void *stream) {
+    DA_REQUIRE(x, "da_train_backward: null argument");
+    return train_backward_impl(w, grads, g, x, nullptr, t, d_out, d_feats, workspace, workspace_bytes, mma_precision, stage, stream);
+}
+
+int da_train_backward_idx(const da_weights *w, const da_weights *grads, const da_graph *g, const int32_t *idx,
+                          const int64_t *t, const float *d_logits, float *d_feats, void *workspace, size_t workspace_bytes,
+                          int mma_precision, int stage, void *stream) {
+    DA_REQUIRE(idx, "da_train_backward_idx: null argument");
+    return train_backward_impl(w, grads, g, nullptr, idx, t, d_logits, d_feats, workspace, workspace_bytes, mma_precision, stage, stream);
+}
+
 int da_train_backward(const da_weights *w, const da_weights *grads, const da_graph *g, const float *x,
                       const int64_t *t, const float *d_out, float *d_feats, void *workspace, size_t workspace_bytes,
                       void *stream) {
@@ -1379,16 +1427,19 @@ int da_train_backward_ex(const da_weights *w, const da_weights *grads, const da_
 // exchange of that bucket -- 1.7 M of the 3.2 M parameters -- can then run on a side stream under the largest dW / dX products
 // of the step, conv 0's, and the mlp / embedding tail): DA_TRAIN_BWD_EARLY = head, convs L-1 .. 1; DA_TRAIN_BWD_LATE = conv 0,
 // virtual-node embedding, mlp, concat pieces.  EARLY then LATE on one stream == DA_TRAIN_BWD_ALL, launch for launch.
-int da_train_backward_stage(const da_weights *w, const da_weights *grads, const da_graph *g, const float *x,
-                            const int64_t *t, const float *d_out, float *d_feats, void *workspace, size_t workspace_bytes,
-                            int mma_precision, int stage, void *stream) {
+static int train_backward_impl(const da_weights *w, const da_weights *grads, const da_graph *g, const float *x, const int32_t *idx,
+                               const int64_t *t, const float *d_out, float *d_feats, void *workspace, size_t workspace_bytes,
+                               int mma_precision, int stage, void *stream) {
     Dims d;
     DA_REQUIRE(stage == DA_TRAIN_BWD_ALL || stage == DA_TRAIN_BWD_EARLY || stage == DA_TRAIN_BWD_LATE, "da_train_backward_stage: unknown stage %d", stage);
     const bool do_early = stage != DA_TRAIN_BWD_LATE, do_late = stage != DA_TRAIN_BWD_EARLY;
     int rc;
     DA_REQUIRE(mma_precision == DA_TRAIN_MMA_FP32 || mma_precision == DA_TRAIN_MMA_BF16, "da_train_backward: unknown mma_precision %d", mma_precision);
     if ((rc = dims_of(w, g, d, mma_precision))) return rc;
-    DA_REQUIRE(grads && x && t && d_out && workspace, "da_train_backward: null argument");
+    DA_REQUIRE(idx || !d.disc, "da_train_backward: a discrete denoiser takes position indices (da_train_backward_idx)");
+    DA_REQUIRE(!idx || d.disc, "da_train_backward_idx: not a discrete denoiser (da_train_backward_stage takes poses)");
+    DA_REQUIRE(grads && (x || idx) && t && d_out && workspace, "da_train_backward: null argument");
+    DA_REQUIRE(!d.disc || (grads->variant == DA_VARIANT_DISCRETE && grads->c_out == w->c_out && grads->pos_w1), "da_train_backward_idx: grads must mirror the discrete weights");
     DA_REQUIRE(d.dense || (d.gcn && gcn_plan_kind(g) != 2) || (g->out_ptr && (g->out_dst || d.hybrid)), "da_train_backward: the graph needs the by-source CSR (out_ptr / "
                "out_dst; of the remainder edges for hybrid graphs, where out_dst may be empty)");
     if ((rc = check_fused(w, d, "da_train_backward(weights)"))) return rc;
@@ -1495,6 +1546,10 @@ int da_train_backward_stage(const da_weights *w, const da_weights *grads, const 
     }
     k_time_scatter<<<(((nr + 15) / 16) * 32 + 255) / 256, 256, 0, st>>>(nr, D, d.F, w->steps, t, ws.dcomb, G(grads->time_emb));
     DA_LAUNCH_CHECK();
+    if (d.disc) {          // the lookup's gradient: one owner per table row, fixed order (da_d3pm_train.hip); no pos_mlp products
+        if ((rc = launch_embed_idx_grad(nr, d.c_out, D, d.F, idx, ws.dcomb, G(grads->pos_w1), st))) return rc;
+        return join_side();
+    }
     // pos_mlp (efficient_gat.py:133): Linear(c,16) GELU Linear(16,32); the hidden layer is recomputed
     k_pos_hidden<<<(nr * 16 + 255) / 256, 256, 0, st>>>(nr, d.c_in, x, w->pos_w0, w->pos_b0, ws.pa, ws.p1);
     DA_LAUNCH_CHECK();

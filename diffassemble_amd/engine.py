@@ -383,8 +383,8 @@ class DenoiserEngine:
             self._seed.copy_(torch.tensor([_wrap64(seed), _wrap64(offset)], dtype=torch.int64))
         return self._seed
 
-    def d3pm_noise(self, seed, iteration, n, K):
-        return d3pm_noise(seed, iteration, n, K)
+    def d3pm_noise(self, seed, iteration, n, K, domain="sampling"):
+        return d3pm_noise(seed, iteration, n, K, domain)
 
     def d3pm_step(self, sched: Schedule, x_t, logits, t, ratio, noise=None, seed=None, iteration=0, return_post=False):
         return d3pm_step(sched, x_t, logits, t, ratio, noise=noise, seed=seed, iteration=iteration, return_post=return_post)
@@ -578,13 +578,60 @@ class DenoiserEngine:
 
 
 # ---------------------------------------------------------------------- kernel-level helpers
-def d3pm_noise(seed, iteration, n, K):
-    """The uniforms the discrete reverse step draws for itself from ``seed`` (int64 [2] device tensor {seed, offset}): [n, K] fp32
-    in (0, 1] (da_d3pm_noise)."""
+def d3pm_noise(seed, iteration, n, K, domain="sampling"):
+    """The uniforms the discrete reverse step (``domain="sampling"``) or the training-side noising of ``d3pm_q_sample``
+    (``domain="training"``) draws for itself from ``seed`` (int64 [2] device tensor {seed, offset}): [n, K] fp32 in (0, 1]
+    (da_d3pm_noise_ex).  The two domains never share a stream."""
     u = torch.empty((n, K), dtype=torch.float32, device=seed.device)
+    dom = {"sampling": _lib.D3PM_DRAW_SAMPLING, "training": _lib.D3PM_DRAW_TRAINING}[domain]
     with torch.cuda.device(seed.device):
-        _lib.check(_lib.lib().da_d3pm_noise(_lib.ptr(seed), int(iteration), int(n), int(K), _lib.ptr(u), _lib.stream_ptr(seed.device)))
+        _lib.check(_lib.lib().da_d3pm_noise_ex(_lib.ptr(seed), int(iteration), int(n), int(K), dom, _lib.ptr(u), _lib.stream_ptr(seed.device)))
     return u
+
+
+def d3pm_q_sample(sched: Schedule, x_start, t, K, noise=None, seed=None, iteration=0):
+    """The discrete forward noising (da_d3pm_q_sample, spatial_diffusion_discrete.py:181-191 in closed form): x_start [N] indices,
+    t [N] int64 on a ROCm device -> x_t [N] int64.  ``noise`` [N, K] uniforms (parity tests), or ``seed`` (int64 [2] device tensor)
+    for the kernel's own draw in the training domain -- no [N, K] buffer is made."""
+    dev = x_start.device
+    if dev.type != "cuda":
+        raise _lib.DaError("d3pm_q_sample needs ROCm tensors (no CPU path in diffassemble_amd)")
+    x0 = x_start.detach().to(device=dev, dtype=torch.int32).contiguous()
+    tt = t.detach().to(device=dev, dtype=torch.int64).contiguous()
+    nz = None if noise is None else _f32(noise, dev)
+    n = x0.shape[0]
+    if tt.shape != (n,) or (nz is not None and nz.shape != (n, int(K))):
+        raise _lib.DaError(f"d3pm_q_sample: shapes x_start {tuple(x0.shape)}, t {tuple(tt.shape)}, noise {None if nz is None else tuple(nz.shape)}, K {K}")
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().da_d3pm_q_sample(C.byref(sched.c), n, int(K), _lib.ptr(x0), _lib.ptr(tt), _lib.ptr(nz), _lib.ptr(seed),
+                                               int(iteration), _lib.ptr(out), _lib.stream_ptr(dev)))
+    return out.long()
+
+
+def d3pm_loss(sched: Schedule, logits, x_start, x_t, t, kind="vb", lambda_loss=0.01):
+    """The loss of the discrete p_losses and its gradient with respect to the logits in one call (da_d3pm_loss): logits [N, K] fp32,
+    x_start / x_t [N] indices, t [N] int64 on a ROCm device; kind "vb" | "cross_entropy" | "hybrid" (lambda_loss * ce + vb).
+    Returns (loss [3] = {total, vb, ce}, d_logits [N, K] for a unit upstream gradient, row_terms [N, 2] = per-piece {vb, ce})."""
+    dev = logits.device
+    if dev.type != "cuda":
+        raise _lib.DaError("d3pm_loss needs ROCm tensors (no CPU path in diffassemble_amd)")
+    if kind not in _lib.D3PM_LOSS:
+        raise _lib.DaError(f"d3pm_loss: kind {kind!r} is not one of {sorted(_lib.D3PM_LOSS)}")
+    z = _f32(logits, dev)
+    n, K = z.shape
+    x0 = x_start.detach().to(device=dev, dtype=torch.int32).contiguous()
+    xt = x_t.detach().to(device=dev, dtype=torch.int32).contiguous()
+    tt = t.detach().to(device=dev, dtype=torch.int64).contiguous()
+    if not (x0.shape == xt.shape == tt.shape == (n,)):
+        raise _lib.DaError(f"d3pm_loss: logits {tuple(z.shape)} against x_start {tuple(x0.shape)}, x_t {tuple(xt.shape)}, t {tuple(tt.shape)}")
+    loss = torch.empty(3, dtype=torch.float32, device=dev)
+    d_logits = torch.empty_like(z)
+    rows = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().da_d3pm_loss(C.byref(sched.c), n, K, _lib.D3PM_LOSS[kind], float(lambda_loss), _lib.ptr(z), _lib.ptr(x0),
+                                           _lib.ptr(xt), _lib.ptr(tt), _lib.ptr(loss), _lib.ptr(d_logits), _lib.ptr(rows), _lib.stream_ptr(dev)))
+    return loss, d_logits, rows
 
 
 def d3pm_step(sched: Schedule, x_t, logits, t, ratio, noise=None, seed=None, iteration=0, return_post=False):

@@ -1,7 +1,6 @@
 """Counterpart of puzzle_diff/model/backbones/__init__.py:1-8 (minus the import of the
-missing ``backbone_vist`` file).  The hot-path denoisers are real (``Eff_GAT_Discrete``:
-inference only); the ablation architectures the drivers merely import are placeholders that
-fail on construction (out of scope)."""
+missing ``backbone_vist`` file).  The hot-path denoisers are real, inference and training;
+the ablation architectures the drivers merely import are placeholders that fail on construction (out of scope)."""
 from .efficient_gat import Eff_GAT
 from .efficient_gat_3d import Eff_GAT_3d
 from .efficient_gat_discrete import Eff_GAT_Discrete

@@ -1,7 +1,8 @@
 """Counterpart of puzzle_diff/model/backbones/efficient_gat_discrete.py (``Eff_GAT_Discrete``): the denoiser of the discrete
 position diffusion.  Same constructor arguments, attribute and state-dict names; ``forward_with_feats`` runs as ONE call into
-the HIP library (embedding lookup -> mlp -> 4x graph attention -> residual -> K-wide logits head).  Inference only: the
-training path of the discrete model is not built."""
+the HIP library (embedding lookup -> mlp -> 4x graph attention -> residual -> K-wide logits head).  Under grad (``train()`` mode
+with trainable parameters) the forward and its backward run through ``DenoiserTrainFn`` over da_train_forward_idx /
+da_train_backward_idx: the indices get no gradient, ``patch_feats`` get theirs when they require it."""
 import torch
 import torch.nn as nn
 from torch import Tensor
@@ -41,7 +42,7 @@ class Eff_GAT_Discrete(DenoiserBase):
     def forward_with_feats(self, xy_pos: Tensor, time: Tensor, patch_rgb: Tensor, edge_index: Tensor, patch_feats: Tensor, batch):
         """efficient_gat_discrete.py:72-97 -> (logits [N, K] fp32, attentions).  ``xy_pos``: position indices [N]."""
         if self._wants_grad():
-            raise NotImplementedError("discrete training is not built yet")
+            return self._run_train(xy_pos, time, edge_index, patch_feats, batch)
         with torch.no_grad():
             return self._run_idx(xy_pos, time, edge_index, patch_feats, batch)
 

@@ -1,12 +1,15 @@
 """Counterpart of puzzle_diff/model/spatial_diffusion_discrete.py: ``GNN_Diffusion`` of the discrete position diffusion (D3PM
 with the uniform transition over ``backbones.Eff_GAT_Discrete``), with the reference's constructor, attributes and Lightning
-hooks.  INFERENCE is built -- forward, reverse step, the captured sampling loop with classifier-free guidance, validation /
-test / predict steps; the training side (``p_losses``, ``q_sample``, ``vb_terms_bpd``, ``training_step``) raises
-``NotImplementedError``.
+hooks: inference (forward, reverse step, the captured sampling loop with classifier-free guidance, validation / test / predict
+steps) and training (``q_sample``, ``p_losses``, ``vb_terms_bpd``, ``training_step``), both on a ROCm device only -- off the
+device the training methods raise ``NotImplementedError``, as the project has no CPU path.
 
-* ``forward_with_feats`` -> one ``da_denoiser_forward_idx`` call
+* ``forward_with_feats`` -> one ``da_denoiser_forward_idx`` call; under grad ``da_train_forward_idx`` / ``da_train_backward_idx``
 * ``p_sample_ddpm``      -> forward (two under guidance) + ``da_d3pm_step``
 * ``p_sample_loop``      -> ``da_sample_loop_idx``: every iteration enqueued by one C call, replayed as one hipGraph launch
+* ``q_sample``           -> ``da_d3pm_q_sample``: the uniforms are drawn inside the kernel, no [N, K] buffer
+* ``p_losses``           -> noising, the denoiser's training forward, and ``da_d3pm_loss``: the loss and its gradient with respect
+                            to the logits in one call (variational bound, label-smoothed cross entropy, or their hybrid)
 
 Differences from the reference, on purpose:
 * no ``Q_onestep`` / ``Q_onestep_transpose`` / ``overline_Q`` buffers ([steps, K, K] fp32 each: 1.9 GB at K = 900, steps = 600).
@@ -17,7 +20,15 @@ Differences from the reference, on purpose:
   loses digits at steps = 600; the closed form is the exact one);
 * the Gumbel uniforms of the captured loop come from a counter-based generator inside the step kernel (seeded from torch's
   generator once per loop), not from one ``torch.rand`` call per step: the draws differ from the reference's stream;
-* ``validation_step`` dumps no images.
+* ``validation_step`` dumps no images, and ``training_step`` runs no ``batch_idx == 0`` sampling-and-image dump;
+* training: the noising uniforms come from the same counter-based generator (its training domain), seeded from torch's generator
+  once per ``p_losses`` call; the reference's unused ``noise`` argument of ``p_losses`` carries injected [N, K] uniforms, and the
+  extensions ``cfg_rand`` ([G] uniforms of the classifier-free mask) and ``patch_feats`` (encoder bypass) exist for parity runs;
+* K comes from the module: the reference's ``one_hot(x_start)`` infers it from the data and fails on a Batch that lacks index
+  K - 1; here such a Batch trains like any other;
+* with ``classifier_free_prob == 0`` no mask is drawn (the reference draws ``rand(G) > 0``, which drops a puzzle's features with
+  probability 2^-24);
+* the ``+1e-6`` that ``categorical_kl_logits`` adds to both logit vectors cancels inside the softmaxes and is not reproduced.
 """
 import torch
 import torch.nn.functional as F
@@ -27,6 +38,33 @@ from . import spatial_diffusion as sd
 
 _Q_TABLES = ("Q_onestep", "Q_onestep_transpose", "overline_Q")
 _NOT_BUILT = "discrete training is not built yet"
+_OFF_DEVICE = _NOT_BUILT + " off the device: it runs on ROCm tensors only (diffassemble_amd has no CPU path)"
+_LOSS_TYPES = ("vb", "cross_entropy", "hybrid")
+
+
+def _require_device(*tensors):
+    """The training methods' guard: every argument must be a tensor on a ROCm device."""
+    if not tensors or not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
+        raise NotImplementedError(_OFF_DEVICE)
+
+
+class _D3pmLoss(torch.autograd.Function):
+    """The discrete p_losses' loss with its gradient with respect to the logits computed in the SAME call (da_d3pm_loss), like
+    ``spatial_diffusion._FusedLoss``: backward is one scaling by the upstream gradient.  Returns (total, {total, vb, ce})."""
+
+    @staticmethod
+    def forward(ctx, logits, sched, x_start, x_t, t, kind, lambda_loss):
+        from ..engine import d3pm_loss
+        loss, d_logits, _ = d3pm_loss(sched, logits, x_start, x_t, t, kind, lambda_loss)
+        ctx.save_for_backward(d_logits)
+        parts = loss.clone()
+        ctx.mark_non_differentiable(parts)
+        return loss[0].clone(), parts
+
+    @staticmethod
+    def backward(ctx, g, _g_parts):
+        (d_logits,) = ctx.saved_tensors
+        return d_logits * g, None, None, None, None, None, None
 
 
 class GNN_Diffusion(sd.GNN_Diffusion):
@@ -54,18 +92,73 @@ class GNN_Diffusion(sd.GNN_Diffusion):
             state_dict.pop(prefix + k, None)
         return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
-    # ------------------------------------------------------------------ training side: not built
-    def training_step(self, batch, batch_idx):
-        raise NotImplementedError(_NOT_BUILT)
+    # ------------------------------------------------------------------ training side (ROCm device only)
+    def _train_seed_tensor(self, device):
+        """The persistent {seed, offset} pair the noising kernel reads, refilled by one draw from torch's generator per call (what
+        ``DenoiserEngine.seed_tensor`` does for the sampling loop)."""
+        s = getattr(self, "_train_seed", None)
+        if s is None or s.device != device:
+            s = self._train_seed = torch.zeros(2, dtype=torch.int64, device=device)
+        s.random_()
+        return s
 
-    def p_losses(self, *args, **kwargs):
-        raise NotImplementedError(_NOT_BUILT)
+    def training_step(self, batch=None, batch_idx=0):
+        """spatial_diffusion_discrete.py:93-141 without the ``batch_idx == 0`` sampling-and-image dump."""
+        if batch is None or not hasattr(batch, "batch"):
+            raise NotImplementedError(_OFF_DEVICE)
+        _require_device(batch.batch, batch.indexes)
+        batch_size = batch.batch.max().item() + 1
+        t = torch.randint(0, self.steps, (batch_size,), device=self.device).long()
+        new_t = torch.gather(t, 0, batch.batch)
+        loss = self.p_losses(batch.indexes % self.K, new_t, loss_type=self.loss_type, cond=batch.patches, edge_index=batch.edge_index,
+                             batch=batch.batch, patch_feats=getattr(batch, "patch_feats", None))
+        self.log("loss", loss)
+        return loss
 
-    def q_sample(self, *args, **kwargs):
-        raise NotImplementedError(_NOT_BUILT)
+    def q_sample(self, x_start=None, t=None, overline_Q=None, eps=1e-9, noise=None):
+        """spatial_diffusion_discrete.py:181-191 in closed form (da_d3pm_q_sample): ``x_start`` [N] indices (or the reference's one-hot
+        [N, K]), ``t`` [N] -> x_t [N] int64.  ``noise`` (extension): the [N, K] uniforms; default: drawn inside the kernel."""
+        _require_device(x_start, t)
+        if overline_Q is not None or eps != 1e-9:
+            raise NotImplementedError("q_sample: explicit transition tables / another eps are not supported (closed form only)")
+        if x_start.dim() == 2:
+            x_start = x_start.argmax(-1)
+        from ..engine import d3pm_q_sample
+        seed = None if noise is not None else self._train_seed_tensor(x_start.device)
+        return d3pm_q_sample(self._schedule(), x_start, t, self.K, noise=noise, seed=seed)
 
-    def vb_terms_bpd(self, *args, **kwargs):
-        raise NotImplementedError(_NOT_BUILT)
+    def vb_terms_bpd(self, pred_x_start_logits=None, model_logits=None, x_start=None, x_t=None, t=None, K=None, overline_Q=None):
+        """spatial_diffusion_discrete.py:416-472 (da_d3pm_loss, kind vb): mean over the pieces of KL(q(x_{t-1} | x_t, x_0) ||
+        p(x_{t-1} | x_t)) / ln 2, the decoder NLL where t == 0; differentiable with respect to ``pred_x_start_logits``.
+        ``model_logits`` is accepted for the reference's signature and not read: the kernel forms the model posterior from the
+        predicted logits itself (q_posterior_logits at previous_t = t - 1)."""
+        _require_device(pred_x_start_logits, x_start, x_t, t)
+        if overline_Q is not None or (K is not None and K != self.K):
+            raise NotImplementedError("vb_terms_bpd: explicit transition tables / another K are not supported (closed form only)")
+        return _D3pmLoss.apply(pred_x_start_logits, self._schedule(), x_start, x_t, t, "vb", float(self.lambda_loss))[0]
+
+    def p_losses(self, x_start=None, t=None, noise=None, loss_type="l1", cond=None, edge_index=None, batch=None, cfg_rand=None,
+                 patch_feats=None):
+        """spatial_diffusion_discrete.py:229-273.  ``x_start`` [N] position indices, ``t`` [N].  ``noise`` (unused by the reference):
+        the [N, K] uniforms of the noising for parity runs, default in-kernel draws; ``cfg_rand`` (extension): the [G] uniforms of
+        the classifier-free mask; ``patch_feats`` (extension) bypasses the piece encoder.  The three parts {total, vb, ce} of the
+        last call stay in ``self.last_loss_parts`` (a [3] device tensor)."""
+        _require_device(x_start, t)
+        if loss_type not in _LOSS_TYPES:
+            raise Exception("Loss not implemented %s", loss_type)
+        _require_device(edge_index, batch)
+        x_noisy = self.q_sample(x_start, t, noise=noise)
+        if patch_feats is None:
+            patch_feats = self.visual_features(cond)
+        if cfg_rand is not None or self.classifier_free_prob > 0.0:
+            if cfg_rand is None:
+                cfg_rand = torch.rand(int(batch.max()) + 1, device=batch.device)
+            keep = cfg_rand.to(batch.device)[batch] > self.classifier_free_prob
+            patch_feats = keep[:, None] * patch_feats
+        prediction = self.forward_with_feats(x_noisy, t, cond, edge_index, patch_feats=patch_feats, batch=batch)
+        loss, parts = _D3pmLoss.apply(prediction, self._schedule(), x_start, x_noisy, t, loss_type, float(self.lambda_loss))
+        self.last_loss_parts = parts
+        return loss
 
     # ------------------------------------------------------------------ reverse process
     def q_posterior_logits(self, x_t, x_start_logits, t, previous_t, K=None, overline_Q=None, eps=1e-8, use_x_start_logits=True):

@@ -32,9 +32,12 @@ from .graph_plan import GraphPlan
 
 
 def _param_order(module):
-    """(names in flat-buffer order, number of conv layers); names relative to the Eff_GAT / Eff_GAT_3d module."""
-    names = ["time_emb.weight", "pos_mlp.0.weight", "pos_mlp.0.bias", "pos_mlp.2.weight", "pos_mlp.2.bias",
-             "mlp.0.weight", "mlp.0.bias", "mlp.2.weight", "mlp.2.bias"]
+    """(names in flat-buffer order, number of conv layers); names relative to the Eff_GAT / Eff_GAT_3d / Eff_GAT_Discrete module.
+    The discrete variant has the embedding table ``pos_mlp.weight`` [K, 32] where the pose MLP's four tensors were, and a K-row
+    ``final_mlp.2``."""
+    pos = ["pos_mlp.weight"] if getattr(module, "variant", "2d") == "discrete" else \
+        ["pos_mlp.0.weight", "pos_mlp.0.bias", "pos_mlp.2.weight", "pos_mlp.2.bias"]
+    names = ["time_emb.weight"] + pos + ["mlp.0.weight", "mlp.0.bias", "mlp.2.weight", "mlp.2.bias"]
     n_layers = len(module.gnn_backbone.module_list)
     # (the virtual-node embedding sits in FRONT of the convs: its gradient is produced after conv 0's, so it belongs to the
     #  late bucket of the data-parallel exchange -- everything before conv 1 -- see TrainEngine.backward)
@@ -58,7 +61,7 @@ def _param_order(module):
 
 
 class TrainEngine:
-    """Owns the flat buffers + training workspace of one ``Eff_GAT`` / ``Eff_GAT_3d`` module on one GPU."""
+    """Owns the flat buffers + training workspace of one ``Eff_GAT`` / ``Eff_GAT_3d`` / ``Eff_GAT_Discrete`` module on one GPU."""
 
     def __init__(self, module, device=None):
         self.lib = _lib.lib()
@@ -103,7 +106,7 @@ class TrainEngine:
         by = dict(zip(names, self.views))
         self.D = by["mlp.0.weight"].shape[1]
         self.F = self.D - 64
-        self.c_in = by["pos_mlp.0.weight"].shape[1]
+        self.c_in = 1 if self.variant == "discrete" else by["pos_mlp.0.weight"].shape[1]      # discrete: one position index per piece
         self.c_out = 7 if self.variant == "3d" else by["final_mlp.2.weight"].shape[0]        # 3D: unit quaternion wxyz | translation
         self.steps = by["time_emb.weight"].shape[0]
         self.hidden = by["mlp.0.weight"].shape[0]
@@ -160,14 +163,17 @@ class TrainEngine:
 
     def _weights_struct(self, by):
         w = _lib.DaWeights()
-        w.variant = _lib.VARIANT_3D if self.variant == "3d" else _lib.VARIANT_2D
+        w.variant = {"3d": _lib.VARIANT_3D, "discrete": _lib.VARIANT_DISCRETE}.get(self.variant, _lib.VARIANT_2D)
         w.arch = {"exophormer": _lib.ARCH_EXOPHORMER, "gcn": _lib.ARCH_GCN}.get(self.arch, _lib.ARCH_TRANSFORMER)
         w.steps, w.c_in, w.c_out, w.feat_dim, w.hidden = self.steps, self.c_in, self.c_out, self.F, self.hidden
         w.heads, w.n_layers, w.virt_nodes = 8, self.n_layers, self.virt_nodes
         P = lambda n: by[n].data_ptr()  # noqa: E731
         w.time_emb = P("time_emb.weight")
-        w.pos_w0, w.pos_b0, w.pos_w1, w.pos_b1 = (P("pos_mlp.0.weight"), P("pos_mlp.0.bias"), P("pos_mlp.2.weight"),
-                                                  P("pos_mlp.2.bias"))
+        if self.variant == "discrete":
+            w.pos_w1 = P("pos_mlp.weight")                 # [K, 32]; pos_w0 / pos_b0 / pos_b1 stay NULL (da_weights, DA_VARIANT_DISCRETE)
+        else:
+            w.pos_w0, w.pos_b0, w.pos_w1, w.pos_b1 = (P("pos_mlp.0.weight"), P("pos_mlp.0.bias"), P("pos_mlp.2.weight"),
+                                                      P("pos_mlp.2.bias"))
         w.mlp_w0, w.mlp_b0, w.mlp_w1, w.mlp_b1 = (P("mlp.0.weight"), P("mlp.0.bias"), P("mlp.2.weight"),
                                                   P("mlp.2.bias"))
         for l in range(self.n_layers):
@@ -240,17 +246,20 @@ class TrainEngine:
         return self._ws
 
     def forward(self, plan: GraphPlan, x, t, feats):
-        """da_train_forward: out [n_real, c_out] fp32; activations stay in the workspace for backward."""
-        x = x.detach().to(self.device, torch.float32).contiguous()
+        """da_train_forward: out [n_real, c_out] fp32; activations stay in the workspace for backward.  Discrete variant: ``x``
+        holds the position indices [n_real] and ``out`` the logits [n_real, K] (da_train_forward_idx)."""
+        disc = self.variant == "discrete"
+        x = x.detach().to(self.device, torch.int32 if disc else torch.float32).contiguous()
         t = t.detach().to(self.device, torch.int64).contiguous()
         feats = feats.detach().to(self.device, torch.float32).contiguous()
-        assert x.shape == (plan.n_real, self.c_in) and feats.shape == (plan.n_real, self.F), (x.shape, feats.shape)
+        assert x.shape == ((plan.n_real,) if disc else (plan.n_real, self.c_in)) and feats.shape == (plan.n_real, self.F), (x.shape, feats.shape)
         out = torch.empty((plan.n_real, self.c_out), dtype=torch.float32, device=self.device)
         ws = self._workspace(plan)
         g = self._cg(plan)
+        fwd = self.lib.da_train_forward_idx if disc else self.lib.da_train_forward_ex
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.da_train_forward_ex(C.byref(self.w), C.byref(g), _lib.ptr(x), _lib.ptr(t), _lib.ptr(feats),
-                                                    _lib.ptr(out), _lib.ptr(ws), ws.numel(), self._mma(), _lib.stream_ptr(self.device)))
+            _lib.check(fwd(C.byref(self.w), C.byref(g), _lib.ptr(x), _lib.ptr(t), _lib.ptr(feats),
+                           _lib.ptr(out), _lib.ptr(ws), ws.numel(), self._mma(), _lib.stream_ptr(self.device)))
         self._fwd_mma = self._mma()
         return out
 
@@ -276,9 +285,11 @@ class TrainEngine:
         if not attached:
             self.flat_grad.zero_()
         self.grads_synced = False
-        x = x.detach().to(self.device, torch.float32).contiguous()
+        disc = self.variant == "discrete"
+        x = x.detach().to(self.device, torch.int32 if disc else torch.float32).contiguous()
         t = t.detach().to(self.device, torch.int64).contiguous()
         d_out = d_out.detach().to(self.device, torch.float32).contiguous()
+        bwd = self.lib.da_train_backward_idx if disc else self.lib.da_train_backward_stage
         d_feats = torch.empty((plan.n_real, self.F), dtype=torch.float32, device=self.device) if want_dfeats else None
         mma = getattr(self, "_fwd_mma", self._mma())       # the mode of the forward it follows
         ws = self._workspace(plan, mma)
@@ -287,9 +298,9 @@ class TrainEngine:
         staged = overlap or getattr(self, "force_staged", False)       # (force_staged: tests -- the two halves without a process group)
         with torch.cuda.device(self.device):
             for stage in ((_lib.TRAIN_BWD_EARLY, _lib.TRAIN_BWD_LATE) if staged else (_lib.TRAIN_BWD_ALL,)):
-                _lib.check(self.lib.da_train_backward_stage(C.byref(self.w), C.byref(self.gw), C.byref(g), _lib.ptr(x), _lib.ptr(t),
-                                                            _lib.ptr(d_out), _lib.ptr(d_feats), _lib.ptr(ws), ws.numel(), mma, stage,
-                                                            _lib.stream_ptr(self.device)))
+                _lib.check(bwd(C.byref(self.w), C.byref(self.gw), C.byref(g), _lib.ptr(x), _lib.ptr(t),
+                               _lib.ptr(d_out), _lib.ptr(d_feats), _lib.ptr(ws), ws.numel(), mma, stage,
+                               _lib.stream_ptr(self.device)))
                 if stage == _lib.TRAIN_BWD_EARLY and overlap:
                     self._exchange_early()
         if not attached:
@@ -299,7 +310,8 @@ class TrainEngine:
 
 
 class DenoiserTrainFn(torch.autograd.Function):
-    """out = Eff_GAT.forward_with_feats(x, t, feats) with the backward in the HIP library.  Parameter gradients are
+    """out = Eff_GAT.forward_with_feats(x, t, feats) with the backward in the HIP library (``x``: poses, or the position indices of
+    ``Eff_GAT_Discrete`` -- integer, so autograd asks no gradient for them).  Parameter gradients are
     written straight into ``TrainEngine.flat_grad`` (aliased by ``param.grad``), not returned to autograd.
 
     ONE parameter -- the ``anchor`` (the engine's smallest tensor) -- is passed as an autograd input and receives a ZERO

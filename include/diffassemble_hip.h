@@ -381,6 +381,10 @@ int da_d3pm_step(const da_schedule *s, int n, int K, const int32_t *x_t, const f
  * Philox4x32-10, key = the two halves of seed[0], counter = (r K + k + seed[1] as 64 bits, iteration, a constant),
  * u = ((bits >> 8) + 1) 2^-24 in (0, 1].  u [n, K] fp32.                                                                  */
 int da_d3pm_noise(const uint64_t *seed, int iteration, int n, int K, float *u, void *stream);
+/* ... and of a named draw DOMAIN (additive to ABI 19): the reverse step's Gumbel uniforms (da_d3pm_noise) or the training-side
+ * noising of da_d3pm_q_sample.  The two use different counter constants, so one seed never gives both the same stream.  */
+enum { DA_D3PM_DRAW_SAMPLING = 0, DA_D3PM_DRAW_TRAINING = 1 };
+int da_d3pm_noise_ex(const uint64_t *seed, int iteration, int n, int K, int domain, float *u, void *stream);
 
 /* The whole discrete sampling loop == p_sample_loop (spatial_diffusion_discrete.py:324-356): for i in reversed(range(0, steps,
  * ratio)): forward (a second one over zero piece features under classifier-free guidance, logits = (1 + w) cond - w uncond,
@@ -566,6 +570,46 @@ int da_train_backward_stage(const da_weights *w, const da_weights *grads, const 
 int da_q_sample(int steps, int n, int c, const float *sqrt_alphas_cumprod, const float *sqrt_one_minus_alphas_cumprod,
                 const float *x_start, const float *noise, const int64_t *t, float *x_noisy, void *stream);
 int da_loss_grad(int kind, size_t n, const float *target, const float *pred, float *loss, float *d_pred, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Training of the discrete position model (additive to ABI 19): spatial_diffusion_discrete.py's q_sample (:181-191), p_losses
+ * (:229-273), vb_terms_bpd (:416-472) with q_posterior_logits (:193-227) at previous_t = t - 1 and categorical_kl_logits
+ * (:475-488), in the closed form of the uniform transition (no [steps, K, K] table; a_t = alphas_cumprod[t]); fp32, 2 <= K <= 1024,
+ * one wave per piece, indices and timesteps clamped as in da_d3pm_step.
+ *
+ * da_d3pm_q_sample: x_noisy[r] = argmax_k( log(a_t [k == x_start[r]] + (1 - a_t) / K + 1e-9)
+ *                                          - log(-log(clip(u[r, k], FLT_MIN, 1))) ), the lowest index wins a tie, the inner
+ *   -log u floored at 2^-25 as in da_d3pm_step.  noise [n, K] uniforms (parity tests), or NULL: drawn inside the kernel from
+ *   `seed` (device {seed, offset}) and `iteration` in the DA_D3PM_DRAW_TRAINING domain -- no [n, K] buffer exists.
+ *
+ * da_d3pm_loss: the loss of p_losses AND its gradient with respect to the logits z (for a unit upstream gradient), per piece with
+ *   pi = softmax(z), p = t - 1, r = a_t / a_p, c1 = ((a_p - a_t) / a_p) / K, c2 = (1 - a_p) / K, eps = 1e-8:
+ *     t > 0 : m[k]  = log(r [k == x_t] + c1 + eps) + log(a_p pi[k] + c2 + eps)                 model posterior logits
+ *             q~[k] = log(r [k == x_t] + c1 + eps) + log(a_p [k == x_start] + c2 + eps)       true posterior logits
+ *             vb_row = KL(softmax(q~) || softmax(m)) / ln 2      (q from its at most four distinct values)
+ *     t == 0: vb_row = -log_softmax(z)[x_start] / ln 2                                        (decoder NLL)
+ *     ce_row = -sum_k y[k] log pi[k], y = 0.99 e_{x_start} + 0.01 / K                         (F.cross_entropy, label_smoothing 1e-2)
+ *   kind DA_D3PM_LOSS_VB: mean vb_row | _CE: mean ce_row | _HYBRID: lambda mean ce_row + mean vb_row.
+ *   loss [3] = {total, mean vb_row, mean ce_row} (a term the kind does not use reads 0); d_logits [n, K] = d total / d z;
+ *   row_terms [n, 2] receives {vb_row, ce_row} and feeds the finishing reduction: one workgroup, fixed order, no float atomics.
+ *   (The +1e-6 categorical_kl_logits adds to both logit vectors cancels inside the softmaxes and is not reproduced.)          */
+enum { DA_D3PM_LOSS_VB = 0, DA_D3PM_LOSS_CE = 1, DA_D3PM_LOSS_HYBRID = 2 };
+int da_d3pm_q_sample(const da_schedule *s, int n, int K, const int32_t *x_start, const int64_t *t, const float *noise,
+                     const uint64_t *seed, int iteration, int32_t *x_noisy, void *stream);
+int da_d3pm_loss(const da_schedule *s, int n, int K, int kind, float lambda, const float *logits, const int32_t *x_start,
+                 const int32_t *x_t, const int64_t *t, float *loss, float *d_logits, float *row_terms, void *stream);
+/* The discrete denoiser's training forward / backward: da_train_forward_ex / da_train_backward_stage with position indices
+ * idx [n_real] int32 where the poses were.  w->variant must be DA_VARIANT_DISCRETE (c_in = 1, c_out = K, arch =
+ * DA_ARCH_TRANSFORMER, pos_w1 = pos_mlp.weight [K, 32], pos_w0 / pos_b0 / pos_b1 NULL); the float-pose entries above reject that
+ * variant, these reject the others.  out / d_out: logits [n_real, K] and their gradient (caller's buffers: the workspace holds
+ * no [n, K] image).  The embedding gradient pos_mlp.weight.grad[idx[r]] += d comb[r, F : F + 32] has one owner per table row
+ * and a fixed summation order: it is bit-reproducible.  DA_TRAIN_BWD_EARLY / _LATE keep their meaning (head early,
+ * embeddings late); workspace size from da_train_workspace_bytes_ex.                                                        */
+int da_train_forward_idx(const da_weights *w, const da_graph *g, const int32_t *idx, const int64_t *t, const float *feats,
+                         float *logits, void *workspace, size_t workspace_bytes, int mma_precision, void *stream);
+int da_train_backward_idx(const da_weights *w, const da_weights *grads, const da_graph *g, const int32_t *idx,
+                          const int64_t *t, const float *d_logits, float *d_feats, void *workspace, size_t workspace_bytes,
+                          int mma_precision, int stage, void *stream);
 
 /* The 3D model's training glue (additive to ABI 19):
  *   da_head3d_backward  the pose head's backward on its own: pre [n, 6] = [r | t] (what the head's second Linear layers
