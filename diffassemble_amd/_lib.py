@@ -26,7 +26,8 @@ TRAIN_BWD_ALL, TRAIN_BWD_EARLY, TRAIN_BWD_LATE = 0, 1, 2
 D3PM_DRAW_SAMPLING, D3PM_DRAW_TRAINING = 0, 1
 D3PM_LOSS = {"vb": 0, "cross_entropy": 1, "hybrid": 2}
 DBG_COUNTERS = ("opt_gen_workgroups", "dense_fast_exits", "dual_gen_slabs", "opt_masked_gen_workgroups")          # fallback events (indices 0 .. 3)
-DBG_LAUNCH_COUNTERS = {"resident_launches": 4, "virtual_rows_in_launch": 5}          # which kernel took a layer (DA_DBG_RES_LAUNCHES, DA_DBG_VIRT_IN_LAUNCH)
+DBG_LAUNCH_COUNTERS = {"resident_launches": 4, "virtual_rows_in_launch": 5,           # which kernel took a layer (DA_DBG_RES_LAUNCHES, DA_DBG_VIRT_IN_LAUNCH,
+                       "resident_projection_launches": 6}                              # DA_DBG_RES_PROJ_LAUNCHES)
 PROF_CLASSES = ("embed", "linear_mlp", "linear_qkvs", "attn_hidden", "attn_last", "head", "update", "conv_fused")
 
 _fp = C.c_void_p        # device pointers travel as integers

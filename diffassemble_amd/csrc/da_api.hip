@@ -103,6 +103,8 @@ struct da_denoiser {
     void *conv0c_wd = nullptr, *virt_qkvs_d = nullptr;      // their dense-path variants (Q pre-scaled, see ConvW)
     void *conv0c_wdp = nullptr, *convLf_wp = nullptr;       // conv0c_wd / convLf_w packed for the row-panel kernel (see ConvW::wdp)
     void *conv0c_wqs = nullptr;                             // conv0c_wd's per-head fragments (see ConvW::wqs)
+    bool attn_qsf = false;            // disable_folds bit 64 was clear when this denoiser was created: the wqs images exist, hidden layers of large complete
+                                      // graphs are projected by their attention kernel (a later da_config_set changes neither)
     float *conv0c_bd = nullptr;
     bool q_prescaled = false;
     // ... and the LAST conv's value / skip projections are folded with final_mlp.0 (its consumer, linear up to
@@ -530,7 +532,8 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
                     xin = dst; ldx = c.hc;
                     continue;
                 }
-                rc = timed(d, last ? DA_PROF_ATTN_LAST : DA_PROF_ATTN_HIDDEN, st, [&] {
+                // (a layer projected by its attention kernel is ONE kernel: priced as such, projection + attention FLOP, Q | K | V | skip never in HBM)
+                rc = timed(d, qsf ? DA_PROF_CONV_FUSED : (last ? DA_PROF_ATTN_LAST : DA_PROF_ATTN_HIDDEN), st, [&] {
                     return launch_attn_dense(prec, L, d->heads, c.C, g->n_graphs, g->max_graph_nodes, g->graph_ptr,
                                              g->pad_ptr, g->dense == 2, resid, act, dst, st); });
                 if (rc > 0) return rc;
@@ -747,10 +750,9 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
         return p;
     };
     // per-head Q / skip fragments of a hidden layer's dense-path projection (bf16, 32-wide heads, K = 128 / 256); nullptr otherwise
+    d->attn_qsf = attn_qsf_enabled();
     auto pack_qs = [&](const void *wsrc, int K, int hc, int C) -> void * {
-#ifndef DA_EXPERIMENTS
-        return nullptr;          // (k_attn_res<.., 64> lost its A/B: experiments build only)
-#endif
+        if (!d->attn_qsf) return nullptr;
         if (precision != DA_PREC_BF16 || C != 32 || H != 8 || (K != 128 && K != 256) || !wsrc || mfma_disabled()) return nullptr;
         void *p = alloc(w_qs_bytes(H, K));
         if (!p || pack_w_qs(H, K, hc, wsrc, p, st)) { rc = 2; return nullptr; }
@@ -1373,10 +1375,10 @@ int da_conv_dense_ex(int prec, const da_graph *g, int heads, int C, int Din, con
     qs.Cv = folded ? 32 : 0;
     const int nout = folded ? 2 * (int)hc + heads * 32 : 4 * (int)hc;
     // the layer form the sampling loop takes for hidden layers of large complete graphs (run_forward): the projection happens in the prologue of
-    // the resident attention kernel; its per-head weight fragments are packed into the scratch's (then unused) K region
-    const bool qsf = !folded && !residual && !g->hybrid && g->n_nodes == g->n_real && b && w_qs_bytes(heads, Din) <= hb &&
+    // the resident attention kernel; its per-head weight fragments are packed into the scratch's (then unused, adjacent) K and V regions
+    const bool qsf = attn_qsf_enabled() && !folded && !residual && !g->hybrid && g->n_nodes == g->n_real && b && w_qs_bytes(heads, Din) <= 2 * hb &&
                      attn_qsf_applicable(prec, heads, C, Din, g->n_graphs, g->max_graph_nodes, g->n_pad, (flags & DA_CONV_Q_PRESCALED) ? 1 : 0);
-    void *wq_img = base + hb;                        // (the K region of the scratch: K | V stay in the CU)
+    void *wq_img = base + hb;                        // (the K | V regions of the scratch: K | V stay in the CU)
     int rc = 0;
     if (qsf) {
         if ((rc = pack_w_qs(heads, Din, (int)hc, w, wq_img, st))) return rc;
@@ -1409,6 +1411,7 @@ int da_debug_counters(int64_t *out, int n, int reset) {
     out[DA_DBG_DUAL_GEN_SLABS] = (int64_t)b2[0];
     out[DA_DBG_OPT_MASKED_GEN_WORKGROUPS] = (int64_t)a[2];
     out[DA_DBG_RES_LAUNCHES] = (int64_t)da::attn_res_launches(reset);
+    out[DA_DBG_RES_PROJ_LAUNCHES] = (int64_t)da::attn_res_qsf_launches(reset);
     out[DA_DBG_VIRT_IN_LAUNCH] = (int64_t)da::attn_virt_launches(reset);
     return 0;
 }

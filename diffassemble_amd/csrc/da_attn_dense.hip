@@ -929,6 +929,10 @@ bool attn_qsf_applicable(int prec, int heads, int C, int kin, int n_graphs, int 
     if ((size_t)C * (size_t)n_pad * 2 >= ((size_t)1 << 31)) return false;
     return attn_res_qsf_shape_ok(max_graph_nodes, n_pad, n_graphs, kin);
 }
+bool attn_qsf_enabled() {          // (experiments build: DA_ATTN_RES_QSF=0 / 1 overrides the switch)
+    const int x = DA_XENV("DA_ATTN_RES_QSF", -1);
+    return x < 0 ? !(cfg().disable_folds & DA_FOLD_ATTN_PROJ) : x != 0;
+}
 
 // da_debug_counters: [0] k_attn_opt workgroups re-run in GEN mode, [1] k_attn_dense waves that left FAST mode, since the last reset
 int attn_dense_counters(unsigned long long *out4, int reset) {

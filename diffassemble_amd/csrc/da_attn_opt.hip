@@ -903,6 +903,15 @@ static int launch_optt(AttnDenseParams p, hipStream_t st) {
 // global memory (lane (i, half) owns channels 8 jj + 4 half .. + 3 of query i: 8-byte skip loads and stores) -- no LDS staging,
 // no workgroup barrier per slab.  32 puzzles x 8 heads = 256 workgroups = one per CU.  Reference: the same TransformerConv
 // attention (backbones/Transformer_GNN.py:32).
+// projection in the prologue (k_attn_res<.., 64>): where the Q and skip blocks' weight fragments (2 KS KB) start out.  Inside the K | V image, in its
+// last stages, when those lie behind the eight stages the waves' first slabs fill; otherwise behind everything else (image, 512 B of words, the K and
+// V blocks' fragments, 128 bias floats)
+template <int KS>
+__host__ __device__ static inline int res_qsf_qs_off(int max_nodes) {
+    const int img = ((max_nodes + 63) >> 6) * OptK<32, 64>::STAGE;
+    return img >= 8 * OptK<32, 64>::STAGE + 2 * KS * 1024 ? img - 2 * KS * 1024 : img + 512 + 2 * KS * 1024 + 512;
+}
+
 template <int NWV, bool QUEUE, bool KPF, int XV = 0>
 __global__ __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : ((NWV > 5 || (XV & 8)) ? 4 : 5)) void k_attn_res(AttnDenseParams p) {
     // XV (experiments, A/B through DA_ATTN_RES_PH): bit 0 = two PV accumulators (keys 0 .. 15 / 16 .. 31 of every block: no product waits for
@@ -926,9 +935,12 @@ __global__ __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : ((NWV > 5 || (XV & 8)) ? 
     // while nothing else is going on in the CU: wave w takes the 32-node slabs w and w + 16.  x rows come from global memory in operand shape
     // (lane (node, half), k-step s: x[node][16 s + 8 half .. + 7]), the head's four 32 x KIN weight blocks are A operands out of LDS (pack_w_qs
     // image: MFMA row a = channel pi(a), bits 2 and 3 swapped, so registers 8 t .. 8 t + 7 of a lane are the 16-byte chunk 2 t + half of its
-    // node's row -- in every layout that follows).  The Q and skip weights sit in the last stages of the image, which slabs >= 16 fill last: rows to p.Q / p.S in the
+    // node's row -- in every layout that follows).  The Q and skip weights sit in the last stages of the image, which slabs >= 16 fill last (graphs whose
+    // image is too short for that -- below 12 stages at a reduction of 256, 10 at 128 -- leave room for them BEHIND the image instead): rows to p.Q / p.S in the
     // projection kernels' own layouts -- the loop below reads them back as it always did; a wave's first slab keeps its Q fragments in
     // registers -- then K and V straight into the resident LDS image (K chunks swizzled, V row-major), where the DMA burst used to put them.
+    // Slab w + 16's x rows are requested INSIDE slab w's last (V) chain, fragment by fragment into the registers that chain has just read for the last time: their
+    // round trip runs under the rest of the chain and the LDS stores behind it instead of between two matrix phases with every wave of the CU waiting.
     // Three barriers, all in front of the key loop.  Same 16-step MFMA chain, bias after the reduction, same rounding as the projection
     // kernels: every row is the two-kernel path's bit for bit.  (A wave projecting the NEXT slab's Q and skip between two slabs instead -- the
     // first form of this variant -- costs ~5 us per slab: the loop is bound by each wave's own latency chain, and a second chain of global
@@ -986,7 +998,7 @@ __global__ __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : ((NWV > 5 || (XV & 8)) ? 
         // pack_w_qs image of head h: blocks Q, K, V, skip, KS KB each
         const unsigned char *wsrc = (const unsigned char *)p.wqs + (size_t)h * 4 * KS * 1024;
         const unsigned wl = lds0 + (unsigned)(wimg - smem);
-        const int qs_off = ((p.max_nodes + 63) >> 6) * STAGE - 2 * KS * 1024;          // the Q / skip blocks: the last 2 KS KB of the (still empty) image
+        const int qs_off = res_qsf_qs_off<KS>(p.max_nodes);
         for (int j = wid; j < 4 * KS; j += NWV) {
             const int blk = j / KS, s_ = j - blk * KS;           // wave-uniform
             const unsigned dst = (blk == 1 || blk == 2) ? wl + (unsigned)(((blk - 1) * KS + s_) * 1024) : lds0 + (unsigned)(qs_off + ((blk ? 1 : 0) * KS + s_) * 1024);
@@ -1069,30 +1081,47 @@ __global__ __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : ((NWV > 5 || (XV & 8)) ? 
     static_assert(!PROG || CF::NCH == 2, "progressive landing: two Q fragments per lane");
     // ---- QSF: the projection prologue (see the header of the kernel)
     [[maybe_unused]] u32x4 xq[KS];          // a slab's x rows, every k-step (one memory round trip per slab)
-    [[maybe_unused]] auto x_issue = [&](int sl) {
+    [[maybe_unused]] const int xstep = p.debug == 77 ? 1024 : 32;          // bytes between a lane's fragments of consecutive k-steps
+    [[maybe_unused]] auto x_row = [&](int sl) {
         const int nd = max(min(sl * 32 + i, n_g - 1), 0);          // (rows behind the graph repeat its last row: finite K / V rows, never stored Q / skip rows)
         const unsigned char *row = (const unsigned char *)p.x + ((size_t)(node0 + nd) * (size_t)p.ldx + 8 * half) * 2;
         // (p.debug == 77, timing only, WRONG results: the same bytes as 1 KB-contiguous loads, as if x were stored fragment-major)
         if (p.debug == 77) row = (const unsigned char *)p.x + ((size_t)(node0 + max(min(sl * 32, n_g - 32), 0)) * (size_t)p.ldx) * 2 + lane * 16;
-#pragma unroll
-        for (int s_ = 0; s_ < KS; ++s_) xq[s_] = *(const u32x4 *)(row + s_ * (p.debug == 77 ? 1024 : 32));
+        return row;
     };
-    // two chains over the slab's x fragments: a0 = W0 x^T, a1 = W1 x^T (channel x node); weight fragments one k-step ahead of their products
-    [[maybe_unused]] auto chain2 = [&](const unsigned char *w0b, const unsigned char *w1b, f32x16 &a0, f32x16 &a1) {
-        unsigned lo = (unsigned)lane * 16u;
-        asm volatile("" : "+v"(lo));          // (keeps the weight-fragment reads where they are used: hoisted they are 128 registers)
+    [[maybe_unused]] auto x_issue = [&](int sl) {
+        const unsigned char *row = x_row(sl);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { a0[r] = 0.f; a1[r] = 0.f; }
-        u32x4 wa0 = *(const u32x4 *)(w0b + lo), wa1 = *(const u32x4 *)(w1b + lo);
+        for (int s_ = 0; s_ < KS; ++s_) xq[s_] = *(const u32x4 *)(row + s_ * xstep);
+    };
+    // One chain over the slab's x fragments: a = W x^T (channel x node), one 32 x KIN weight block at a time, its fragments one k-step ahead of their
+    // products.  (One accumulator, not two side by side: a chain of this instruction issues back to back on its own, and 24 registers fewer -- an
+    // accumulator and its weight fragments -- is what keeps the prologue inside the 128 registers of a sixteen-wave workgroup; with two, the first
+    // form of this prologue spilled 44 of them.)  Reload (the slab's LAST chain only): nxt = the x row of this lane in the wave's next slab;
+    // fragment s is requested into xq[s] right behind the product that read the old one for the last time, in straight-line code, so that the
+    // compiler's waits in the next slab's first chain count per fragment: every fragment has a whole chain's time to arrive.
+    struct Reload { enum { value = 1 }; };
+    struct NoReload { enum { value = 0 }; };
+    typedef const __attribute__((address_space(1))) u32x4 *xptr_t;
+    [[maybe_unused]] auto chain1 = [&](auto rl, const unsigned char *wb, f32x16 &a, const unsigned char *nxt = nullptr) {
+        unsigned lo = (unsigned)lane * 16u;
+        asm volatile("" : "+v"(lo));          // (keeps the weight-fragment reads where they are used: hoisted they are 64 registers)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) a[r] = 0.f;
+        u32x4 wa = *(const u32x4 *)(wb + lo);
 #pragma unroll
         for (int s_ = 0; s_ < KS; ++s_) {
-            u32x4 wn0 = wa0, wn1 = wa1;
-            if (s_ + 1 < KS) { wn0 = *(const u32x4 *)(w0b + (size_t)(s_ + 1) * 1024 + lo); wn1 = *(const u32x4 *)(w1b + (size_t)(s_ + 1) * 1024 + lo); }
+            u32x4 wn = wa;
+            if (s_ + 1 < KS) wn = *(const u32x4 *)(wb + (size_t)(s_ + 1) * 1024 + lo);
             __builtin_amdgcn_sched_barrier(0);
-            a0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wa0), __builtin_bit_cast(bf16x8, xq[s_]), a0, 0, 0, 0);
-            a1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wa1), __builtin_bit_cast(bf16x8, xq[s_]), a1, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wa), __builtin_bit_cast(bf16x8, xq[s_]), a, 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            wa0 = wn0; wa1 = wn1;
+            if constexpr (decltype(rl)::value) {
+                asm volatile("" : "+v"(nxt));             // (one address pair, stepped here: computed ahead, the sixteen addresses are 32 registers)
+                xq[s_] = *(xptr_t)(size_t)nxt;
+                nxt += xstep;
+            }
+            wa = wn;
         }
     };
     // chunk t (of this lane's two: 2 t + half) of a projected row: accumulator registers 8 t .. 8 t + 7 + bias, rounded to bf16
@@ -1105,34 +1134,38 @@ __global__ __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : ((NWV > 5 || (XV & 8)) ? 
     };
     // Q and skip rows of slab sl (xq holds it) -> memory, in the projection kernels' layouts; keep = this wave's first slab: its Q fragments stay in qf
     [[maybe_unused]] auto project_qs = [&](int sl, bool keep) {
-        f32x16 aQ, aS;
-        const unsigned char *wq_ = smem + (size_t)(((p.max_nodes + 63) >> 6) * STAGE - 2 * KS * 1024);
-        chain2(wq_, wq_ + (size_t)KS * 1024, aQ, aS);
+        const unsigned char *wq_ = smem + (size_t)res_qsf_qs_off<KS>(p.max_nodes);
         const int row = sl * 32 + i;
+        f32x16 a;
+        chain1(NoReload(), wq_, a);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const u32x4 qc = chunk_of(aQ, 0, t), sc_ = chunk_of(aS, 3, t);
+            const u32x4 qc = chunk_of(a, 0, t);
             if (keep) qf[t] = qc;
-            if (row < n_g) {
-                *(u32x4 *)(const_cast<unsigned char *>(Qg) + (size_t)row * CF::ROWB + (2 * t + half) * 16) = qc;
-                *(u32x4 *)((unsigned char *)p.S + ((size_t)(node0 + row) * HC + (size_t)h * C) * 2 + (2 * t + half) * 16) = sc_;
-            }
+            if (row < n_g) *(u32x4 *)(const_cast<unsigned char *>(Qg) + (size_t)row * CF::ROWB + (2 * t + half) * 16) = qc;
+        }
+        chain1(NoReload(), wq_ + (size_t)KS * 1024, a);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const u32x4 sc_ = chunk_of(a, 3, t);
+            if (row < n_g) *(u32x4 *)((unsigned char *)p.S + ((size_t)(node0 + row) * HC + (size_t)h * C) * 2 + (2 * t + half) * 16) = sc_;
         }
     };
-    // K and V rows of slab sl (xq holds it) -> the resident image (stage sl / 2: K rows with the chunk swizzle of the DMA image, V rows behind them)
-    [[maybe_unused]] auto project_kv = [&](int sl) {
-        f32x16 aK, aV;
-        chain2(wimg, wimg + (size_t)KS * 1024, aK, aV);
+    // K and V rows of slab sl (xq holds it) -> the resident image (stage sl / 2: K rows with the chunk swizzle of the DMA image, V rows behind them);
+    // the V chain is the slab's last: Reload requests the next slab's x rows there
+    [[maybe_unused]] auto project_kv = [&](auto rl, int sl, const unsigned char *nxt = nullptr) {
         const int rt = (sl & 1) * 32 + i;          // row inside the 64-key stage
         unsigned char *st_ = smem + (size_t)(sl >> 1) * STAGE + (size_t)rt * 64;
+        f32x16 a;
+        chain1(NoReload(), wimg, a);
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            *(u32x4 *)(st_ + (((2 * t + half) ^ KG::f(rt)) << 4)) = chunk_of(aK, 1, t);
-            *(u32x4 *)(st_ + KG::KBYTES + ((2 * t + half) << 4)) = chunk_of(aV, 2, t);
-        }
+        for (int t = 0; t < 2; ++t) *(u32x4 *)(st_ + (((2 * t + half) ^ KG::f(rt)) << 4)) = chunk_of(a, 1, t);
+        chain1(rl, wimg + (size_t)KS * 1024, a, nxt);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) *(u32x4 *)(st_ + KG::KBYTES + ((2 * t + half) << 4)) = chunk_of(a, 2, t);
     };
-    if constexpr (QSF) x_issue(slab);
-    else if constexpr (!PROG) load_q(slab, qf);    else if constexpr (!PROG) load_q(slab, qf);
+    if constexpr (QSF) { if (slab < nslab) x_issue(slab); }          // (a wave without a slab requests nothing: no pending load on its path to the barriers)
+    else if constexpr (!PROG) load_q(slab, qf);
     // PROG: this wave's pieces (tiles t0p, t0p + 2, ...: nmine of them, issued in that order, with nothing older than them outstanding but the two
     // Q loads above and nothing younger) and how many it has posted
     [[maybe_unused]] const int t0p = wid >> 3, nmine = nkt > t0p ? (nkt - t0p + 1) >> 1 : 0;
@@ -1184,11 +1217,18 @@ __global__ __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : ((NWV > 5 || (XV & 8)) ? 
         // weight fragments, bias words and slab A's x rows are there; barrier 1
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        // slab A (= wave index: stages 0 .. 7 of the image) completely, then Q / skip of slab B; every x row is read ONCE per workgroup
-        if (hasA) { project_qs(slab, true); project_kv(slab); }
-        if (hasB) { x_issue(slabB); project_qs(slabB, false); }
-        __builtin_amdgcn_s_barrier();          // 2: nobody reads the Q / skip weights (in the last stages of the K | V image) any more
-        if (hasB) project_kv(slabB);
+        // slab A (= wave index: stages 0 .. 7 of the image) completely -- its K | V chain requests slab B's x rows as it goes -- then Q / skip of
+        // slab B; every x row is read ONCE per workgroup
+        // (slab B's Q / skip chains sit INSIDE the branch that requested its rows: reachable on one path only, their waits are exact counts)
+        if (hasA) {
+            project_qs(slab, true);
+            if (hasB) { project_kv(Reload(), slab, x_row(slabB)); project_qs(slabB, false); }
+            else project_kv(NoReload(), slab);
+        }
+        // 2: nobody reads the Q / skip weights any more (WAR: in the last stages of the K | V image, which slabs B are about to fill; where they sit
+        // behind the image the barrier orders nothing, but no graph that small has a slab B worth a second code path: 16 .. 21 slabs)
+        __builtin_amdgcn_s_barrier();
+        if (hasB) project_kv(NoReload(), slabB);
         // the Q / skip rows have reached the L2, the K | V rows the LDS; barrier 3, the last one of the kernel
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -1578,22 +1618,27 @@ static long long g_res_launches = 0;       // da_debug_counters [DA_DBG_RES_LAUN
 long long attn_res_launches(int reset) {
     return reset ? __atomic_exchange_n(&g_res_launches, 0ll, __ATOMIC_RELAXED) : __atomic_load_n(&g_res_launches, __ATOMIC_RELAXED);
 }
+static long long g_res_qsf_launches = 0;   // [DA_DBG_RES_PROJ_LAUNCHES]: those of them that did their layer's projection themselves (no projection kernel ran)
+long long attn_res_qsf_launches(int reset) {
+    return reset ? __atomic_exchange_n(&g_res_qsf_launches, 0ll, __ATOMIC_RELAXED) : __atomic_load_n(&g_res_qsf_launches, __ATOMIC_RELAXED);
+}
 
-// projection in the prologue (k_attn_res<16, true, true, 64 (+ 128)>): LDS = the K | V tiles + 512 B of words + two weight blocks + 128 bias floats
-// (the other two weight blocks start out inside the K | V image: it must hold them -- 2 kin / 16 KB <= four 8 KB stages at kin = 256)
-static size_t attn_res_qsf_lds(int max_nodes, int kin) { return (size_t)((max_nodes + 63) >> 6) * OptK<32, 64>::STAGE + 512 + (size_t)2 * (kin >> 4) * 1024 + 512; }
+// projection in the prologue (k_attn_res<16, true, true, 64 (+ 128)>): LDS = the K | V tiles + 512 B of words + two weight blocks + 128 bias floats;
+// the other two weight blocks start out inside the K | V image where it is long enough, behind the bias floats where it is not (res_qsf_qs_off)
+static size_t attn_res_qsf_lds(int max_nodes, int kin) {
+    const size_t img = (size_t)((max_nodes + 63) >> 6) * OptK<32, 64>::STAGE, wb = (size_t)2 * (kin >> 4) * 1024, base = img + 512 + wb + 512;
+    const size_t qs = (size_t)(kin == 128 ? res_qsf_qs_off<8>(max_nodes) : res_qsf_qs_off<16>(max_nodes));
+    return qs >= img ? qs + wb : base;
+}
 static bool attn_res_takes(int max_nodes, int n_pad, int n_graphs) {          // launch_attn_opt's test for the resident kernel (complete graphs)
     return cfg().attn_level >= 2 && DA_XENV("DA_OPT_HID", 0) == 0 && max_nodes >= DA_XENV("DA_ATTN_RES_MIN", 512) && max_nodes <= 19 * 64 &&
            (long long)n_pad * 2 >= (long long)n_graphs * max_nodes;
 }
+// the shapes k_attn_res<.., 64> takes (whether a caller ASKS for it is the caller's switch: da_config.disable_folds bit 64, attn_qsf_enabled)
 bool attn_res_qsf_shape_ok(int max_nodes, int n_pad, int n_graphs, int kin) {
-#ifndef DA_EXPERIMENTS
-    return false;          // (the instance exists in the experiments build only)
-#endif
-    if (!DA_XENV("DA_ATTN_RES_QSF", 0) || (kin != 128 && kin != 256)) return false;
-    if (DA_XENV("DA_ATTN_RES_PH", 1) != 1) return false;
-    return attn_res_takes(max_nodes, n_pad, n_graphs) && attn_res_qsf_lds(max_nodes, kin) <= (size_t)160 * 1024 &&
-           (size_t)((max_nodes + 63) >> 6) * OptK<32, 64>::STAGE >= (size_t)8 * OptK<32, 64>::STAGE + (size_t)2 * (kin >> 4) * 1024;
+    if (kin != 128 && kin != 256) return false;
+    if (DA_XENV("DA_ATTN_RES_PH", 1) != 1 || DA_XENV("DA_ATTN_RES_PIPE", 0) != 0) return false;
+    return attn_res_takes(max_nodes, n_pad, n_graphs) && attn_res_qsf_lds(max_nodes, kin) <= (size_t)160 * 1024;
 }
 
 // Fragment-major image of a layer's projection weights for k_attn_res<.., 64>: packed[((h * 4 + m) * KS + s) * 64 + lane] = the 16 bytes
@@ -1675,17 +1720,17 @@ int launch_attn_opt(const AttnDenseParams &p, int C, hipStream_t st) {
                                       : launch_res<5, false, true>(p, st);          // 12 x 12 puzzles: five slabs, five waves, four workgroups per CU (96 VGPRs)
 #endif
             if (res && v == 0 && p.max_nodes >= res_min && p.max_nodes <= 19 * 64 /* 19 stages + the queue word <= 160 KB */ && (long long)p.n_pad * 2 >= (long long)p.n_graphs * p.max_nodes) {
-#ifdef DA_EXPERIMENTS
-                // OPT-IN (DA_ATTN_RES_QSF=1): the layer's projection in this kernel's prologue.  Bit-identical to the two-kernel path; measured on the
-                // headline (profiles/r06/r06_prologue_projection_*.log): the three hidden layers' kernels 294 -> 287 us per branch-step, the STEP
-                // +2.5 % (0.668 -> 0.686 ms) -- in the two-graph loop the projection kernels already run under the other branch's attention, the
-                // longer attention kernel does not; with x loads as 1 KB-contiguous instructions (timing probe, DA_QSF_FAKE_FM=1) 268 us and -1.2 %.
+                // DEFAULT where the caller sets p.x (da_config.disable_folds bit 64 clear): the layer's projection in this kernel's prologue.
+                // Bit-identical to the two-kernel path.  Round 6 measured the first form on the headline (profiles/r06/r06_prologue_projection_*.log):
+                // the STEP +2.5 % with a prologue that spilled 44 registers and waited for its second slab's rows between two matrix phases; this
+                // form (110 registers, the second slab's rows requested inside the first slab's last chain): -3.8 % / -4.2 % at 20 / 100-step loops,
+                // 12 of 12 interleaved pairs each (DESIGN.md "Measured, round 10", profiles/r10/NOTES.md).
                 if (p.x) {
                     DA_REQUIRE(attn_res_qsf_shape_ok(p.max_nodes, p.n_pad, p.n_graphs, p.kin) && p.wqs && p.bias_q && p.bias_k && p.bias_v && p.bias_s,
                                "k_attn_res: projection in the prologue requested for a shape it does not take");
+                    __atomic_fetch_add(&g_res_qsf_launches, 1ll, __ATOMIC_RELAXED);
                     return p.kin == 256 ? launch_res<16, true, true, 64>(p, st) : launch_res<16, true, true, 64 + 128>(p, st);
                 }
-#endif
 #ifdef DA_EXPERIMENTS
                 switch (DA_XENV("DA_ATTN_RES_PH", 1)) {          // A/B switches; default 1
                     case 3: return launch_res<16, false, true>(p, st);         // fixed slabs (wave, wave + 16)

@@ -153,6 +153,10 @@ struct DenseLayout {
 };
 // da_attn_dense.hip / da_attn_opt.hip: whether launch_attn_dense will take the resident kernel's projection-in-the-prologue form for this layer
 bool attn_qsf_applicable(int prec, int heads, int C, int kin, int n_graphs, int max_graph_nodes, int n_pad, int q_prescaled);
+// the switch: da_config.disable_folds bit 64 (DA_FOLD_ATTN_PROJ) clear, the default (experiments build: DA_ATTN_RES_QSF=0 / 1 overrides).  A denoiser
+// asks ONCE, when it is created, like for every other fold (da_denoiser::attn_qsf: it packs the weight image then or never); da_conv_dense_ex, which
+// keeps nothing between calls, asks per call
+bool attn_qsf_enabled();
 size_t w_qs_bytes(int heads, int kin);
 int pack_w_qs(int heads, int kin, int hc, const void *wd, void *packed, hipStream_t st);
 // wpacked: optional fragment-major copy of W (pack_w_xpanel) for the row-panel kernel (da_gemm_xpanel.hip)
@@ -207,6 +211,7 @@ int launch_attn_dual(const DenseLayout &L, int heads, int C, int n_graphs, int m
 int attn_dense_counters(unsigned long long *out4, int reset);
 long long attn_virt_launches(int reset);     // da_attn_opt.hip: masked hidden-layer launches that carried the virtual rows
 long long attn_res_launches(int reset);      // da_attn_opt.hip: launches of the K / V-resident kernel since the last reset
+long long attn_res_qsf_launches(int reset);  // ... those of them that projected their layer themselves
 int attn_dual_counters(unsigned long long *out2, int reset);
 // hybrid mode: the rows the masked kernel does not own (virtual nodes) over their remainder edges
 int launch_attn_csr_cont(int prec, int n_nodes, int n_real, const int32_t *irr_row_ptr, const int32_t *irr_col_src,

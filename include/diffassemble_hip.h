@@ -60,7 +60,8 @@ typedef struct da_config {
     int32_t disable_folds;       /* DA_DISABLE_FOLDS=<bits>: 1 mlp.2 composed into its consumers, 2 folded last      */
                                  /* layer, 4 softmax scale inside Wq, 8 DDIM update inside the head kernel,          */
                                  /* 16 one-kernel tail, 32 virtual rows on a side stream / inside the masked         */
-                                 /* attention's launch (hybrid graphs)                                               */
+                                 /* attention's launch (hybrid graphs), 64 a hidden layer's Q|K|V|skip projection in */
+                                 /* the prologue of its K/V-resident attention kernel (no projection kernel)         */
     int32_t attn_level;          /* DA_ATTN_LEVEL: 0 = the general dense kernel only, 1 = + the optimistic ring      */
                                  /* kernels, 2 = + the K/V-resident hidden-layer kernel (default)                    */
     int32_t xpanel;              /* DA_ENABLE_XPANEL: -1 = row-panel projections for large Batches (largest graph    */
@@ -486,6 +487,8 @@ enum {
     DA_DBG_RES_LAUNCHES = 4,               /* launches of the K / V-resident hidden-layer kernel (k_attn_res; its    */
                                            /* per-WAVE re-runs count under DA_DBG_OPT_GEN_WORKGROUPS)                */
     DA_DBG_VIRT_IN_LAUNCH = 5,             /* masked hidden-layer launches that carried the exophormer's virtual rows */
+    DA_DBG_RES_PROJ_LAUNCHES = 6,          /* k_attn_res launches that projected Q | K | V | skip of their layer in   */
+                                           /* their own prologue (disable_folds bit 64 clear): no projection kernel   */
     DA_DBG_NCOUNTERS = 8
 };
 int da_debug_counters(int64_t *out /* host [n] */, int n, int reset);
