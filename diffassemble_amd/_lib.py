@@ -16,14 +16,14 @@ LIB_PATH = os.environ.get("DA_LIB_PATH") or os.path.join(os.path.dirname(os.path
 DA_MAX_LAYERS = 8
 ABI_VERSION = 19
 PREC_F32, PREC_BF16 = 0, 1
-VARIANT_2D, VARIANT_3D, VARIANT_DISCRETE = 0, 1, 2
+VARIANT_2D, VARIANT_3D, VARIANT_DISCRETE, VARIANT_DISCRETE_ROT = 0, 1, 2, 3
 ARCH_TRANSFORMER, ARCH_EXOPHORMER, ARCH_GCN = 0, 1, 2
 MEAN_EPSILON, MEAN_START_X = 0, 1
 ACT_NONE, ACT_GELU, ACT_LEAKY02 = 0, 1, 2
 CONV_Q_PRESCALED, CONV_FOLDED_V32 = 1, 2
 TRAIN_MMA_FP32, TRAIN_MMA_BF16 = 0, 1
 TRAIN_BWD_ALL, TRAIN_BWD_EARLY, TRAIN_BWD_LATE = 0, 1, 2
-D3PM_DRAW_SAMPLING, D3PM_DRAW_TRAINING = 0, 1
+D3PM_DRAW_SAMPLING, D3PM_DRAW_TRAINING, D3PM_DRAW_SAMPLING_ROT = 0, 1, 2
 D3PM_LOSS = {"vb": 0, "cross_entropy": 1, "hybrid": 2}
 DBG_COUNTERS = ("opt_gen_workgroups", "dense_fast_exits", "dual_gen_slabs", "opt_masked_gen_workgroups")          # fallback events (indices 0 .. 3)
 DBG_LAUNCH_COUNTERS = {"resident_launches": 4, "virtual_rows_in_launch": 5,           # which kernel took a layer (DA_DBG_RES_LAUNCHES, DA_DBG_VIRT_IN_LAUNCH,
@@ -73,6 +73,13 @@ class DaLoopOpts(C.Structure):
 class DaD3pmOpts(C.Structure):
     """da_d3pm_opts: classifier-free guidance switch + weight, injected uniforms [n_iters, n_real, K] or the device {seed, offset} pair."""
     _fields_ = [("cfg", C.c_int32), ("cfg_w", C.c_float), ("noise", C.c_void_p), ("seed", C.c_void_p)]
+
+
+class DaD3pmRotOpts(C.Structure):
+    """da_d3pm_rot_opts: cold diffusion switch, the fixed input indices of ``only_rotation``, injected uniforms [n_iters, n_real, K] /
+    [n_iters, n_real, 4], the device {seed, offset} pair."""
+    _fields_ = [("cold", C.c_int32), ("reserved0", C.c_int32), ("x_fixed", C.c_void_p), ("noise_x", C.c_void_p), ("noise_rot", C.c_void_p),
+                ("seed", C.c_void_p)]
 
 
 class DaSchedule(C.Structure):
@@ -207,6 +214,12 @@ PROTOTYPES = {
                                         _fp, C.c_size_t, C.c_int, C.c_int, _fp]),
     "da_sample_loop_idx": (C.c_int, [_fp, C.POINTER(DaGraph), C.POINTER(DaSchedule), C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t,
                                      C.c_int, C.POINTER(DaD3pmOpts), _fp]),
+    "da_denoiser_set_features_rot": (C.c_int, [_fp, C.POINTER(DaGraph), _fp, _fp, C.c_size_t, _fp]),
+    "da_denoiser_forward_rot": (C.c_int, [_fp, C.POINTER(DaGraph), _fp, _fp, _fp, C.c_int64, _fp, _fp, _fp, C.c_int, _fp, C.c_size_t, _fp]),
+    "da_d3pm_rot_step": (C.c_int, [C.POINTER(DaSchedule), C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, _fp, _fp, _fp, C.c_int,
+                                   _fp, _fp, _fp, _fp, _fp, _fp]),
+    "da_sample_loop_rot": (C.c_int, [_fp, C.POINTER(DaGraph), C.POINTER(DaSchedule), C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                     C.c_size_t, C.c_int, C.POINTER(DaD3pmRotOpts), _fp]),
     "da_profile_enable": (C.c_int, [_fp, C.c_int]),
     "da_profile_read": (C.c_int, [_fp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "da_linear": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int, _fp, _fp,

@@ -74,6 +74,9 @@ struct LoopKey {
     size_t noise_stride;      // the same for opts.noise (two-branch loops read row ranges of one [n_iters, N, c] buffer)
     da_config cfg;            // the switches the graph was recorded under (da_config_set between two calls records a new graph)
     const void *seed;         // da_sample_loop_idx: the device {seed, offset} pair the recorded kernels read (NULL otherwise)
+    // da_sample_loop_rot (mean_type -2): the rotation side's pointers and the cold switch (zero otherwise)
+    const void *rot_init, *rot_traj, *rot_final, *x_fixed, *noise_rot;
+    int cold;
 };
 
 }  // namespace da
@@ -151,6 +154,8 @@ struct Workspace {
     char *head_pre;                   // [n_real, 32] act dtype: residual share of final_mlp.0 (fused_mlp2)
     char *feat_proj;                  // [n_real, hidden] act dtype: mlp.0 over the piece-feature columns (+ bias), once per Batch
     char *feat_proj_unc;              // the same for ZERO features (= the bias, broadcast): the unconditional pass of classifier-free guidance
+    char *feat_proj4;                 // DA_VARIANT_DISCRETE_ROT: the four rotated crops' feat_proj images [4][proj4_stride elements]; a step copies
+    size_t proj4_stride;              // row rot_acc[piece] of them into feat_proj (k_embed_idx_time_rot)
     float *model_out_unc;
     char *dq, *dk, *dvt, *dskip;      // dense path: head-major Q, K, V ([H][n_pad][C] each), row-major skip
     size_t dense_off, dense_bytes;    // [dq, dq + dense_bytes) is zero-filled once per Batch
@@ -179,7 +184,8 @@ static Workspace carve(const da_denoiser *d, const da_graph *g, void *base) {
     w.h = take(nrp * d->hidden * s);
     w.feat_proj = take(nrp * d->hidden * s);
     w.feat_proj_unc = take(nrp * d->hidden * s);
-    w.head_pre = take(nrp * 32 * s);
+    const bool rotv = d->variant == DA_VARIANT_DISCRETE_ROT;
+    w.head_pre = take(nrp * (rotv ? 64 : 32) * s);
     w.pz = take(nrp * 32 * (size_t)d->heads * sizeof(float));
     w.combined = take(np * d->D * s);
     const bool gcn = d->arch == DA_ARCH_GCN;           // (the GCN reads none of the attention buffers: xa / xb / z / combined only)
@@ -212,6 +218,8 @@ static Workspace carve(const da_denoiser *d, const da_graph *g, void *base) {
     w.xbuf0 = (float *)take(nr * 8 * sizeof(float));
     w.xbuf1 = (float *)take(nr * 8 * sizeof(float));
     w.gcn_dinv = d->arch == DA_ARCH_GCN ? (float *)take(n * sizeof(float)) : nullptr;
+    w.proj4_stride = align_up(nrp * d->hidden * s, 256) / s;
+    w.feat_proj4 = take(rotv ? 4 * w.proj4_stride * s : 0);
     w.total = off;
     return w;
 }
@@ -300,6 +308,8 @@ struct DiscreteIn {
     char *hh;               // [n_real, 32] act dtype
     char *pz, *pre;         // [H, n_real, 32], [n_real, 32] act dtype
     int folded;             // out
+    int rot = 0;            // DA_VARIANT_DISCRETE_ROT: hh is [n_real, 64], and the embedding selects the piece's feat_proj row by rot_acc
+    const int32_t *rot_acc = nullptr;       // [n_real] or NULL = image 0
     D3pmRows rows() const { D3pmRows r; if (folded) { r.pz = pz; r.pre = pre; } else r.hh = hh; return r; }
 };
 
@@ -323,6 +333,9 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
     if (disc) {
         disc->folded = 0;
         if ((rc = timed(d, DA_PROF_EMBED, st, [&] {
+                 if (disc->rot)
+                     return launch_embed_idx_time_rot(prec, nr, d->c_out, d->F, D, d->hidden, disc->idx, disc->rot_acc, t, t_scalar, d->steps, d->time_emb,
+                                                      d->pos_w1, w.comb_in, w.feat_proj4, w.proj4_stride, w.feat_proj, st);
                  return launch_embed_idx_time(prec, nr, d->c_out, d->F, D, disc->idx, t, t_scalar, d->steps, d->time_emb, d->pos_w1, w.comb_in, st); }))) return rc;
     } else
     if (!h_ready && (rc = timed(d, DA_PROF_EMBED, st, [&] {
@@ -342,6 +355,7 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
                                                          w.h, d->hidden, nullptr, st, D, uncond ? w.feat_proj_unc : w.feat_proj);
              if (r2 >= 0) return r2;
              if (uncond) { set_error("unconditional pass: the hoisted mlp.0 path is not available for this shape"); return 1; }
+             if (disc && disc->rot) { set_error("discrete rot: the hoisted mlp.0 path is not available for this shape"); return 1; }
              return linear(prec, nr, D, d->hidden, w.comb_in, D, d->mlp_w0, d->mlp_b0, act1, nullptr, w.h, d->hidden, st); }))) return rc;
     // mlp.2 (Linear(128 -> 1152), no activation in 2D) only feeds two linear consumers -- the conv-0 projection
     // and, through the residual, final_mlp.0 -- so for the transformer arch it is folded into their weights at
@@ -564,8 +578,10 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
     char *const hh = disc ? disc->hh : w.hh;
     if (fused) {
         // final_mlp.0(conv_out + combined) = Wf . conv_out + (Wf W2) . h + (Wf b2 + bf): the second term first
+        // (hw: 32 rows of final_mlp.0; the discrete rot variant runs final_mlp.0 | final_mlp_rot.0 as one 64-wide product, as the 3D heads do)
+        const int hw = d->variant == DA_VARIANT_DISCRETE_ROT ? 64 : 32;
         if ((rc = timed(d, DA_PROF_HEAD, st, [&] {
-                 return linear(prec, nr, d->hidden, 32, w.h, d->hidden, d->headc_w, d->headc_b, DA_ACT_NONE, nullptr, w.head_pre, 32, st); }))) return rc;
+                 return linear(prec, nr, d->hidden, hw, w.h, d->hidden, d->headc_w, d->headc_b, DA_ACT_NONE, nullptr, w.head_pre, hw, st); }))) return rc;
         rc = timed(d, DA_PROF_HEAD, st, [&] {
             return launch_gemm_mfma(prec, nr, D, d->head_hidden, w.z, D, d->head_w0, d->head_b0, DA_ACT_GELU, nullptr, hh,
                                     d->head_hidden, nullptr, st, D, w.head_pre); });
@@ -714,21 +730,25 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
     // k_embed_pos_time keeps the pose-MLP weight rows in a fixed register array (da_basic.hip); fail here, not on the first
     // forward or inside a hipGraph capture (the reference uses c_in = 2 / 4 in 2D and 7 in 3D)
     DA_REQUIRE(w->c_in >= 1 && w->c_in <= 8, "da_denoiser_create: c_in = %d outside [1, 8]", w->c_in);
-    DA_REQUIRE(w->variant == DA_VARIANT_2D || w->variant == DA_VARIANT_3D || w->variant == DA_VARIANT_DISCRETE, "bad variant %d", w->variant);
-    const bool discrete = w->variant == DA_VARIANT_DISCRETE;
+    DA_REQUIRE(w->variant == DA_VARIANT_2D || w->variant == DA_VARIANT_3D || w->variant == DA_VARIANT_DISCRETE || w->variant == DA_VARIANT_DISCRETE_ROT,
+               "bad variant %d", w->variant);
+    const bool rotv = w->variant == DA_VARIANT_DISCRETE_ROT;           // Eff_GAT_Discrete_ROT: Eff_GAT_Discrete plus final_mlp_rot
+    const bool discrete = w->variant == DA_VARIANT_DISCRETE || rotv;
     if (discrete) {
         // Eff_GAT_Discrete (efficient_gat_discrete.py:19-51): an index in, K logits out, always the transformer
         DA_REQUIRE(w->c_in == 1, "da_denoiser_create(discrete): c_in must be 1 (one position index per piece), got %d", w->c_in);
         DA_REQUIRE(w->c_out >= 2 && w->c_out <= 1024, "da_denoiser_create(discrete): K = c_out = %d outside [2, 1024]", w->c_out);
         DA_REQUIRE(w->arch == DA_ARCH_TRANSFORMER, "da_denoiser_create(discrete): arch must be DA_ARCH_TRANSFORMER");
         DA_REQUIRE(w->pos_w1 && w->head_w1 && w->head_b1, "da_denoiser_create(discrete): pos_w1 (pos_mlp.weight [K, 32]) / head_w1 / head_b1 missing");
+        DA_REQUIRE(!rotv || (w->head_w0 && w->head_b0 && w->head_r_w0 && w->head_r_b0 && w->head_r_w1 && w->head_r_b1),
+                   "da_denoiser_create(discrete rot): head_w0 / head_b0 or head_r_w0 / head_r_b0 / head_r_w1 / head_r_b1 (final_mlp_rot) missing");
     }
     hipStream_t st = (hipStream_t)stream;
     da_denoiser *d = new da_denoiser();
     d->prec = precision; d->variant = w->variant; d->arch = w->arch; d->steps = w->steps; d->c_in = w->c_in;
     d->c_out = w->c_out; d->F = w->feat_dim; d->D = w->feat_dim + 64; d->hidden = w->hidden; d->heads = w->heads;
     d->n_layers = w->n_layers; d->V = w->arch == DA_ARCH_EXOPHORMER ? w->virt_nodes : 0;
-    d->head_hidden = w->variant == DA_VARIANT_3D ? 512 : 32;
+    d->head_hidden = w->variant == DA_VARIANT_3D ? 512 : (rotv ? 64 : 32);
     const int D = d->D, H = d->heads;
     const size_t s = esize(precision);
     int rc = 0;
@@ -829,6 +849,7 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
         if (!w->virt_emb) { set_error("exophormer: virt_emb missing"); return fail(1); }
         d->virt_emb = pack(w->virt_emb, (size_t)d->V * D);
     }
+    float *hw0 = nullptr;                                  // discrete rot: the two first head layers stacked, fp32
     if (d->variant == DA_VARIANT_3D) {
         char *hp = (char *)alloc(512 * (size_t)D * s + 4096);
         d->head_b0 = (float *)alloc(512 * 4);
@@ -840,6 +861,18 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
         if (hipMemcpyAsync(d->head_b0 + 256, w->head_r_b0, 256 * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
         d->head_w1 = copy_f32(w->head_w1, 3 * 256); d->head_b1 = copy_f32(w->head_b1, 3);
         d->head_r_w1 = copy_f32(w->head_r_w1, 3 * 256); d->head_r_b1 = copy_f32(w->head_r_b1, 3);
+    } else if (rotv) {
+        // final_mlp.0 | final_mlp_rot.0 as one [64, D] product (the 3D variant's mlp_t.0 | mlp_r.0 above); hw0 also feeds the mlp.2 fold below
+        hw0 = (float *)alloc(64 * (size_t)D * 4);
+        d->head_b0 = (float *)alloc(64 * 4);
+        if (!hw0 || !d->head_b0) return fail(2);
+        if (hipMemcpyAsync(hw0, w->head_w0, 32 * (size_t)D * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
+        if (hipMemcpyAsync(hw0 + 32 * (size_t)D, w->head_r_w0, 32 * (size_t)D * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
+        if (hipMemcpyAsync(d->head_b0, w->head_b0, 32 * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
+        if (hipMemcpyAsync(d->head_b0 + 32, w->head_r_b0, 32 * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
+        d->head_w0 = pack(hw0, 64 * (size_t)D);
+        d->head_w1 = copy_f32(w->head_w1, (size_t)w->c_out * 32); d->head_b1 = copy_f32(w->head_b1, w->c_out);
+        d->head_r_w1 = copy_f32(w->head_r_w1, 4 * 32); d->head_r_b1 = copy_f32(w->head_r_b1, 4);
     } else {
         d->head_w0 = pack(w->head_w0, 32 * (size_t)D); d->head_b0 = copy_f32(w->head_b0, 32);
         d->head_w1 = copy_f32(w->head_w1, (size_t)w->c_out * 32); d->head_b1 = copy_f32(w->head_b1, w->c_out);
@@ -854,9 +887,11 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
             const int hid = d->hidden, hc0 = d->conv[0].hc;
             float *w2t = (float *)alloc((size_t)hid * D * 4);                  // W2^T [hidden, D]
             float *cw = (float *)alloc((size_t)4 * hc0 * hid * 4);             // Wcat0 . W2
-            float *hw = (float *)alloc((size_t)32 * hid * 4);                  // Wf0 . W2
+            const int hwn = rotv ? 64 : 32;                                     // rows of the (stacked) first head layer
+            const float *hsrc = rotv ? hw0 : w->head_w0;
+            float *hw = (float *)alloc((size_t)hwn * hid * 4);                 // Wf0 . W2
             d->conv0c_b = (float *)alloc((size_t)4 * hc0 * 4);
-            d->headc_b = (float *)alloc(32 * 4);
+            d->headc_b = (float *)alloc(hwn * 4);
             if (!w2t || !cw || !hw || !d->conv0c_b || !d->headc_b) return fail(2);
             if (launch_transpose_f32(D, hid, w->mlp_w1, w2t, st)) return fail(2);
             const float *ws[4] = {w->conv_wq[0], w->conv_wk[0], w->conv_wv[0], w->conv_ws[0]};
@@ -869,10 +904,10 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
                 if (launch_gemm_simple(DA_PREC_F32, 1, D, hc0, w->mlp_b1, D, ws[k], bs[k], DA_ACT_NONE, nullptr,
                                        d->conv0c_b + (size_t)k * hc0, hc0, st)) return fail(2);
             }
-            if (launch_gemm_simple(DA_PREC_F32, 32, D, hid, w->head_w0, D, w2t, nullptr, DA_ACT_NONE, nullptr, hw, hid, st)) return fail(2);
-            if (launch_gemm_simple(DA_PREC_F32, 1, D, 32, w->mlp_b1, D, w->head_w0, nullptr, DA_ACT_NONE, nullptr, d->headc_b, 32, st)) return fail(2);
+            if (launch_gemm_simple(DA_PREC_F32, hwn, D, hid, hsrc, D, w2t, nullptr, DA_ACT_NONE, nullptr, hw, hid, st)) return fail(2);
+            if (launch_gemm_simple(DA_PREC_F32, 1, D, hwn, w->mlp_b1, D, hsrc, nullptr, DA_ACT_NONE, nullptr, d->headc_b, hwn, st)) return fail(2);
             d->conv0c_w = pack(cw, (size_t)4 * hc0 * hid);
-            d->headc_w = pack(hw, (size_t)32 * hid);
+            d->headc_w = pack(hw, (size_t)hwn * hid);
             d->conv0c_wd = d->conv0c_w; d->conv0c_bd = d->conv0c_b;
             if (d->q_prescaled) {          // dense-path variant: Q rows scaled in fp32, then packed (cw is not used afterwards)
                 d->conv0c_bd = (float *)alloc((size_t)4 * hc0 * 4);
@@ -902,7 +937,9 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
             // last conv: value heads and skip folded with final_mlp.0
             const int L = d->n_layers - 1, hcL = d->conv[L].hc, CL = d->conv[L].C, dinL = d->conv[L].din;
             const bool off2 = (cfg().disable_folds & DA_FOLD_LAST) != 0;
-            if (!off2 && CL == 144 && hcL == D && dinL % 32 == 0 && (d->c_out <= 8 || discrete)) {        // (k_head_fold: 8 outputs per row at most)
+            // (the discrete rot variant does not take this fold: both folded attention kernels exist for 32 value channels only, and its
+            //  stacked head has 64 -- it runs the last layer that disable_folds = 2 selects for the position model)
+            if (!off2 && !rotv && CL == 144 && hcL == D && dinL % 32 == 0 && (d->c_out <= 8 || discrete)) {        // (k_head_fold: 8 outputs per row at most)
                 const int nf = 2 * hcL + H * 32;
                 float *lw = (float *)alloc((size_t)nf * dinL * 4);
                 float *sw = (float *)alloc((size_t)32 * dinL * 4);
@@ -1021,6 +1058,7 @@ int da_denoiser_forward(da_denoiser *d, const da_graph *g, const float *x, const
                         size_t workspace_bytes, void *stream) {
     DA_REQUIRE(d && g && x && out && workspace, "da_denoiser_forward: null argument");
     DA_REQUIRE(d->variant != DA_VARIANT_DISCRETE, "da_denoiser_forward: a discrete denoiser takes position indices (da_denoiser_forward_idx)");
+    DA_REQUIRE(d->variant != DA_VARIANT_DISCRETE_ROT, "da_denoiser_forward: a discrete rot denoiser takes position indices (da_denoiser_forward_rot)");
     int rc = check_graph(d, g);
     if (rc) return rc;
     DA_REQUIRE(!alpha || d->arch != DA_ARCH_GCN, "alpha requested from a GCN denoiser: GCN.forward returns no attention weights (gcn.py:22)");
@@ -1035,6 +1073,7 @@ int da_ddim_step(const da_schedule *s, int variant, int mean_type, int n, int c,
                  int prev_all_nonneg, float eta, const float *noise, float *x_prev, void *stream) {
     DA_REQUIRE(s && x && model_out && x_prev, "da_ddim_step: null argument");
     DA_REQUIRE(variant != DA_VARIANT_DISCRETE, "da_ddim_step: the discrete variant has no pose update (da_d3pm_step)");
+    DA_REQUIRE(variant != DA_VARIANT_DISCRETE_ROT, "da_ddim_step: the discrete rot variant has no pose update (da_d3pm_rot_step)");
     DA_REQUIRE(eta == 0.f || noise, "da_ddim_step: eta > 0 needs noise");
     if (variant == DA_VARIANT_3D) {
         DA_REQUIRE(c == 7, "da_ddim_step(3D): c must be 7");
@@ -1119,6 +1158,7 @@ int da_sample_loop_ex(da_denoiser *d, const da_graph *g, const da_schedule *s, i
                       size_t workspace_bytes, int use_graph, const da_loop_opts *opts, void *stream) {
     DA_REQUIRE(d && g && s && x_init && workspace, "da_sample_loop: null argument");
     DA_REQUIRE(d->variant != DA_VARIANT_DISCRETE, "da_sample_loop: a discrete denoiser samples position indices (da_sample_loop_idx)");
+    DA_REQUIRE(d->variant != DA_VARIANT_DISCRETE_ROT, "da_sample_loop: a discrete rot denoiser samples position indices (da_sample_loop_rot)");
     da_loop_opts o;
     int rc = loop_opts("da_sample_loop_ex", d, opts, &o);
     if (rc) return rc;
@@ -1157,6 +1197,7 @@ int da_sample_loop_pair_ex(da_denoiser *d, const da_schedule *s, int mean_type, 
     DA_REQUIRE(d && s && g_a && g_b && x_init_a && x_init_b && x_final_a && x_final_b && workspace_a && workspace_b,
                "da_sample_loop_pair: null argument");
     DA_REQUIRE(d->variant != DA_VARIANT_DISCRETE, "da_sample_loop_pair: a discrete denoiser samples position indices (da_sample_loop_idx)");
+    DA_REQUIRE(d->variant != DA_VARIANT_DISCRETE_ROT, "da_sample_loop_pair: a discrete rot denoiser samples position indices (da_sample_loop_rot)");
     // the samplers of da_sample_loop_ex on both branches: one option set, half a reads opts->noise, half b noise_b (row ranges
     // of one [n_iters, N, c] draw: the poses then equal the one-branch loop's bit for bit)
     da_loop_opts oa, ob;
@@ -1257,6 +1298,8 @@ int da_sample_loop_pair(da_denoiser *d, const da_schedule *s, int mean_type, int
 int da_denoiser_forward_idx(da_denoiser *d, const da_graph *g, const int32_t *idx, const int64_t *t, int64_t t_scalar, float *logits,
                             float *alpha, int alpha_all_layers, void *workspace, size_t workspace_bytes, void *stream) {
     DA_REQUIRE(d && g && idx && logits && workspace, "da_denoiser_forward_idx: null argument");
+    DA_REQUIRE(d->variant != DA_VARIANT_DISCRETE_ROT, "da_denoiser_forward_idx: a discrete rot denoiser has two heads and four feature images "
+               "(da_denoiser_set_features_rot / da_denoiser_forward_rot)");
     DA_REQUIRE(d->variant == DA_VARIANT_DISCRETE, "da_denoiser_forward_idx: not a discrete denoiser (da_denoiser_forward takes poses)");
     int rc = check_graph(d, g);
     if (rc) return rc;
@@ -1300,6 +1343,7 @@ int da_sample_loop_idx(da_denoiser *d, const da_graph *g, const da_schedule *s, 
                        int32_t *traj, int32_t *idx_final, void *workspace, size_t workspace_bytes, int use_graph, const da_d3pm_opts *opts,
                        void *stream) {
     DA_REQUIRE(d && g && s && idx_init && workspace && opts, "da_sample_loop_idx: null argument");
+    DA_REQUIRE(d->variant != DA_VARIANT_DISCRETE_ROT, "da_sample_loop_idx: a discrete rot denoiser samples positions and rotations (da_sample_loop_rot)");
     DA_REQUIRE(d->variant == DA_VARIANT_DISCRETE, "da_sample_loop_idx: not a discrete denoiser (da_sample_loop takes poses)");
     DA_REQUIRE(inference_ratio >= 1 && s->steps >= 1 && s->alphas_cumprod, "da_sample_loop_idx: bad ratio / schedule");
     DA_REQUIRE(opts->noise || opts->seed, "da_sample_loop_idx: needs the uniforms (opts->noise) or a seed (opts->seed)");
@@ -1321,6 +1365,116 @@ int da_sample_loop_idx(da_denoiser *d, const da_graph *g, const da_schedule *s, 
     ko.cfg = o.cfg; ko.cfg_w = o.cfg_w; ko.noise = o.noise;
     return launch_loop_graph(d, "da_sample_loop_idx",
                              loop_key(g, s, -1, inference_ratio, n_iters, idx_init, traj, idx_final, workspace, workspace_bytes, ko, 0, 0, o.seed), enqueue, st);
+}
+
+// ---------------------------------------------------------------------------------------- discrete position + rotation variant
+// every entry of the variant needs the hoisted mlp.0 product: its per-step feature share IS the addend row the embedding selects
+static int require_rot(const char *who, const da_denoiser *d) {
+    DA_REQUIRE(d->variant == DA_VARIANT_DISCRETE_ROT, "%s: not a discrete rot denoiser (DA_VARIANT_DISCRETE_ROT)", who);
+    DA_REQUIRE(hoisted_mlp0_ok(d), "%s: the hoisted mlp.0 path is not available for this denoiser (da_denoiser_flags bit 3)", who);
+    return 0;
+}
+
+int da_denoiser_set_features_rot(da_denoiser *d, const da_graph *g, const float *feats4, void *workspace, size_t workspace_bytes,
+                                 void *stream) {
+    DA_REQUIRE(d && g && feats4 && workspace, "da_denoiser_set_features_rot: null argument");
+    int rc = require_rot("da_denoiser_set_features_rot", d);
+    if (rc || (rc = check_graph(d, g))) return rc;
+    Workspace w = carve(d, g, workspace);
+    DA_REQUIRE(workspace_bytes >= w.total, "workspace too small: %zu < %zu", workspace_bytes, w.total);
+    hipStream_t st = (hipStream_t)stream;
+    // the F-wide hoist of da_denoiser_set_features once per image (image 0 last: comb_in's feature columns are left holding it)
+    for (int r = 3; r >= 0; --r) {
+        if ((rc = launch_set_feats(d->prec, g->n_real, d->F, d->D, feats4 + (size_t)r * g->n_real * d->F, w.comb_in, st))) return rc;
+        rc = launch_gemm_mfma(d->prec, g->n_real, d->F, d->hidden, w.comb_in, d->D, d->mlp_w0, d->mlp_b0, DA_ACT_NONE, nullptr,
+                              w.feat_proj4 + (size_t)r * w.proj4_stride * esize(d->prec), d->hidden, nullptr, st, d->D, nullptr);
+        if (rc > 0) return rc;
+        DA_REQUIRE(rc == 0, "da_denoiser_set_features_rot: feature projection shape not supported (F=%d)", d->F);
+    }
+    if (w.dense_bytes)      // padded rows / columns of the head-major buffers must be finite
+        DA_CHECK_HIP(hipMemsetAsync((char *)workspace + w.dense_off, 0, w.dense_bytes, st));
+    return 0;
+}
+
+int da_denoiser_forward_rot(da_denoiser *d, const da_graph *g, const int32_t *idx, const int32_t *rot_acc, const int64_t *t,
+                            int64_t t_scalar, float *logits, float *rot_logits, float *alpha, int alpha_all_layers, void *workspace,
+                            size_t workspace_bytes, void *stream) {
+    DA_REQUIRE(d && g && idx && logits && rot_logits && workspace, "da_denoiser_forward_rot: null argument");
+    int rc = require_rot("da_denoiser_forward_rot", d);
+    if (rc || (rc = check_graph(d, g))) return rc;
+    DA_REQUIRE(!alpha || g->edge_id, "alpha requested but graph has no edge_id");
+    Workspace w = carve(d, g, workspace);
+    DA_REQUIRE(workspace_bytes >= w.total, "workspace too small: %zu < %zu", workspace_bytes, w.total);
+    hipStream_t st = (hipStream_t)stream;
+    DiscreteIn di{idx, w.hh, (char *)w.pz, w.head_pre, 0, 1, rot_acc};
+    if ((rc = forward_impl(d, g, nullptr, t, t_scalar, nullptr, alpha, alpha_all_layers, nullptr, w, st, nullptr, false, false, &di))) return rc;
+    return timed(d, DA_PROF_HEAD, st, [&] {
+        return launch_d3pm_rot_tail(d->prec, g->n_real, d->c_out, w.hh, d->head_w1, d->head_b1, d->head_r_w1, d->head_r_b1, nullptr, nullptr,
+                                    logits, rot_logits, nullptr, st); });
+}
+
+static int enqueue_loop_rot(da_denoiser *d, const da_graph *g, const da_schedule *s, int ratio, int n_iters, const int32_t *idx_init,
+                            const int32_t *rot_init, int32_t *traj_idx, int32_t *traj_acc, int32_t *idx_final, int32_t *acc_final,
+                            const Workspace &w, hipStream_t st, const da_d3pm_rot_opts &o) {
+    // p_sample_loop, spatial_diffusion_discrete_rot.py:334-375.  Per step: the embedding (lookup + addend-row select by rot_acc), the shared
+    // body, the 64-wide first head layer, ONE tail kernel.  State without trajectories lives in xbuf0 / xbuf1 (each entry is read and
+    // written by the same wave of the tail kernel, so it is updated in place).
+    const int nr = g->n_real, K = d->c_out;
+    const int first = ((s->steps - 1) / ratio) * ratio;
+    int32_t *const st_idx = (int32_t *)w.xbuf0, *const st_acc = st_idx + nr, *const st_rot = (int32_t *)w.xbuf1;
+    const int32_t *cur = idx_init, *rot = rot_init, *acc = nullptr;          // rot_acc starts at zero: image 0
+    int it = 0, rc;
+    for (int i = first; i >= 0 && it < n_iters; i -= ratio, ++it) {
+        int32_t *nxt = traj_idx ? traj_idx + (size_t)it * nr : st_idx;
+        int32_t *nacc = traj_acc ? traj_acc + (size_t)it * nr : st_acc;
+        const int32_t *in = o.x_fixed ? o.x_fixed : cur;                       // only_rotation: every step starts from the given indices
+        DiscreteIn di{in, w.hh, (char *)w.pz, w.head_pre, 0, 1, acc};
+        if ((rc = forward_impl(d, g, nullptr, nullptr, i, nullptr, nullptr, 0, nullptr, w, st, nullptr, false, false, &di))) return rc;
+        D3pmRotStep sp;
+        sp.s = to_dev(s); sp.x_t = in; sp.rot_t = rot; sp.t_scalar = i; sp.ratio = ratio; sp.iteration = it; sp.seed = o.seed;
+        sp.noise_x = o.noise_x ? o.noise_x + (size_t)it * nr * K : nullptr;
+        sp.noise_rot = o.noise_rot ? o.noise_rot + (size_t)it * nr * 4 : nullptr;
+        sp.x_prev = nxt; sp.cold = o.cold; sp.need_prev = o.cold;              // (rot_prev and its draws only feed the state under cold diffusion)
+        sp.rot_acc_in = acc; sp.rot_next = st_rot; sp.rot_acc_out = nacc;
+        if ((rc = timed(d, DA_PROF_UPDATE, st, [&] {
+                 return launch_d3pm_rot_tail(d->prec, nr, K, w.hh, d->head_w1, d->head_b1, d->head_r_w1, d->head_r_b1, nullptr, nullptr, nullptr,
+                                             nullptr, &sp, st); }))) return rc;
+        cur = nxt; acc = nacc; rot = st_rot;
+    }
+    if (idx_final && cur != idx_final) DA_CHECK_HIP(hipMemcpyAsync(idx_final, cur, (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    if (acc_final && acc && acc != acc_final) DA_CHECK_HIP(hipMemcpyAsync(acc_final, acc, (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int da_sample_loop_rot(da_denoiser *d, const da_graph *g, const da_schedule *s, int inference_ratio, int max_iters, const int32_t *idx_init,
+                       const int32_t *rot_init, int32_t *traj_idx, int32_t *traj_rot_acc, int32_t *idx_final, int32_t *rot_acc_final,
+                       void *workspace, size_t workspace_bytes, int use_graph, const da_d3pm_rot_opts *opts, void *stream) {
+    DA_REQUIRE(d && g && s && idx_init && rot_init && workspace && opts, "da_sample_loop_rot: null argument");
+    int rc = require_rot("da_sample_loop_rot", d);
+    if (rc) return rc;
+    DA_REQUIRE(inference_ratio >= 1 && s->steps >= 1 && s->alphas_cumprod, "da_sample_loop_rot: bad ratio / schedule");
+    da_d3pm_rot_opts o;
+    memset(&o, 0, sizeof(o));
+    o.cold = opts->cold ? 1 : 0; o.x_fixed = opts->x_fixed; o.noise_x = opts->noise_x; o.noise_rot = o.cold ? opts->noise_rot : nullptr;
+    o.seed = opts->seed;
+    DA_REQUIRE((o.noise_x && (o.noise_rot || !o.cold)) || o.seed, "da_sample_loop_rot: needs the uniforms (opts->noise_x, opts->noise_rot) or a seed (opts->seed)");
+    if ((rc = check_graph(d, g))) return rc;
+    Workspace w = carve(d, g, workspace);
+    DA_REQUIRE(workspace_bytes >= w.total, "workspace too small: %zu < %zu", workspace_bytes, w.total);
+    hipStream_t st = (hipStream_t)stream;
+    const int n_iters = loop_iters(s, inference_ratio, max_iters);
+    auto enqueue = [&](hipStream_t on) {
+        return enqueue_loop_rot(d, g, s, inference_ratio, n_iters, idx_init, rot_init, traj_idx, traj_rot_acc, idx_final, rot_acc_final, w, on, o); };
+    // the capture rules of da_sample_loop_ex: eager while profiling, straight into a capture the caller has open
+    if (d->prof_on || stream_is_capturing(st)) use_graph = 0;
+    if (!use_graph) return enqueue(st);
+    da_loop_opts ko;                    // (mean_type -2 marks the position + rotation loop)
+    memset(&ko, 0, sizeof(ko));
+    ko.noise = o.noise_x;
+    LoopKey key = loop_key(g, s, -2, inference_ratio, n_iters, idx_init, traj_idx, idx_final, workspace, workspace_bytes, ko, 0, 0, o.seed);
+    key.rot_init = rot_init; key.rot_traj = traj_rot_acc; key.rot_final = rot_acc_final; key.x_fixed = o.x_fixed; key.noise_rot = o.noise_rot;
+    key.cold = o.cold;
+    return launch_loop_graph(d, "da_sample_loop_rot", key, enqueue, st);
 }
 
 size_t da_attn_dense_scratch_bytes(int prec, const da_graph *g, int heads, int C) {

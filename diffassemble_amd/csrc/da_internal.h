@@ -267,7 +267,10 @@ struct D3pmRows {
 // names the draw's DOMAIN: the reverse step's Gumbel uniforms (the default) and the training-side noising of q_sample
 // (da_d3pm_train.hip) use different words, so one seed never gives the two the same stream.
 constexpr uint32_t D3PM_WORD_SAMPLING = 0xD3B07384u, D3PM_WORD_TRAINING = 0x51ED270Bu;
-inline uint32_t d3pm_domain_word(int domain) { return domain == DA_D3PM_DRAW_TRAINING ? D3PM_WORD_TRAINING : D3PM_WORD_SAMPLING; }
+constexpr uint32_t D3PM_WORD_SAMPLING_ROT = 0x2A65C0F1u;      // the rotation half of the position + rotation model (da_d3pm_rot.hip)
+inline uint32_t d3pm_domain_word(int domain) {
+    return domain == DA_D3PM_DRAW_TRAINING ? D3PM_WORD_TRAINING : domain == DA_D3PM_DRAW_SAMPLING_ROT ? D3PM_WORD_SAMPLING_ROT : D3PM_WORD_SAMPLING;
+}
 __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t ctr, uint32_t iteration, uint32_t word = D3PM_WORD_SAMPLING) {
     uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = iteration, c3 = word;
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
@@ -286,6 +289,34 @@ int launch_embed_idx_grad(int n, int K, int D, int F, const int32_t *idx, const 
 // NULL); logits_out nullable; step == NULL: logits only
 int launch_d3pm_tail(int prec, int n, int K, int H, const D3pmRows *rows_c, const D3pmRows *rows_u, float cfg_w, const float *w2,
                      const float *b2, const float *logits_in, float *logits_out, const D3pmStep *step, hipStream_t st);
+
+// da_d3pm_rot.hip: the position + rotation variant (DA_VARIANT_DISCRETE_ROT).  The embedding lookup of launch_embed_idx_time that also
+// copies row rot_acc[r] of the four hoisted feature projections proj4 [4][img_stride] (rows of `hidden` elements, act dtype) into
+// `sel` [n, hidden], the addend of the K = 64 mlp.0 product; rot_acc NULL = image 0
+int launch_embed_idx_time_rot(int prec, int n, int K, int F, int D, int hidden, const int32_t *idx, const int32_t *rot_acc, const int64_t *t,
+                              int64_t t_scalar, int steps, const float *time_emb, const float *pos_emb, void *comb_in, const void *proj4,
+                              size_t img_stride, void *sel, hipStream_t st);
+struct D3pmRotStep {
+    DeviceSchedule s = {};
+    const int32_t *x_t = nullptr, *rot_t = nullptr;
+    const int64_t *t = nullptr;
+    int64_t t_scalar = 0;
+    int ratio = 1;
+    const float *noise_x = nullptr, *noise_rot = nullptr;      // [n, K] / [n, 4] uniforms of this iteration, or NULL: drawn from `seed`
+    const uint64_t *seed = nullptr;
+    int iteration = 0;
+    int32_t *x_prev = nullptr, *rot_0 = nullptr, *rot_prev = nullptr;       // rot_0 / rot_prev nullable
+    float *post_x = nullptr, *post_rot = nullptr;                           // nullable
+    // the loop's state update: rot_next = cold ? rot_prev : rot_0, rot_acc_out = (rot_acc_in + rot_next) % 4 (rot_acc_in NULL = 0)
+    int cold = 0, need_prev = 1;                                            // need_prev 0: the rotation posterior and its draws are skipped
+    const int32_t *rot_acc_in = nullptr;
+    int32_t *rot_next = nullptr, *rot_acc_out = nullptr;
+};
+// hh [n, 64] post-GELU rows (final_mlp.0 | final_mlp_rot.0) through w2 [K, 32] / wr [4, 32], or given logits (logits_in + rot_logits_in);
+// logits_out / rot_logits_out nullable; step NULL: logits only
+int launch_d3pm_rot_tail(int prec, int n, int K, const void *hh, const float *w2, const float *b2, const float *wr, const float *br,
+                         const float *logits_in, const float *rot_logits_in, float *logits_out, float *rot_logits_out,
+                         const D3pmRotStep *step, hipStream_t st);
 
 // generic linear dispatch (MFMA when the shape allows, else simple)
 int linear(int prec, int M, int K, int Nout, const void *A, int lda, const void *W, const float *bias, int act,

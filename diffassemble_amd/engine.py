@@ -90,7 +90,8 @@ def igso3_trap_table(sqrt_one_minus_alphas_cumprod):
 
 
 class DenoiserEngine:
-    """Packs an ``Eff_GAT`` / ``Eff_GAT_3d`` / ``Eff_GAT_Discrete`` (``variant="discrete"``) state dict (reference key layout,
+    """Packs an ``Eff_GAT`` / ``Eff_GAT_3d`` / ``Eff_GAT_Discrete`` (``variant="discrete"``) / ``Eff_GAT_Discrete_ROT``
+    (``variant="discrete_rot"``) state dict (reference key layout,
     see the key list in DESIGN.md section 1) into the HIP library and runs forward / sampling on it."""
 
     def __init__(self, sd, *, variant="2d", arch="transformer", virt_nodes=0, precision="bf16",
@@ -115,10 +116,10 @@ class DenoiserEngine:
         self.n_layers = len(layers)
         D = sd["mlp.0.weight"].shape[1]
         self.D, self.F = D, D - 64
-        discrete = variant == "discrete"          # Eff_GAT_Discrete: pos_mlp is an Embedding(K, 32), the head is K wide
+        discrete = variant in ("discrete", "discrete_rot")      # Eff_GAT_Discrete(_ROT): pos_mlp is an Embedding(K, 32), the head is K wide
         self.c_in = 1 if discrete else sd["pos_mlp.0.weight"].shape[1]
         self.steps = sd["time_emb.weight"].shape[0]
-        w.variant = {"3d": _lib.VARIANT_3D, "discrete": _lib.VARIANT_DISCRETE}.get(variant, _lib.VARIANT_2D)
+        w.variant = {"3d": _lib.VARIANT_3D, "discrete": _lib.VARIANT_DISCRETE, "discrete_rot": _lib.VARIANT_DISCRETE_ROT}.get(variant, _lib.VARIANT_2D)
         w.arch = {"exophormer": _lib.ARCH_EXOPHORMER, "gcn": _lib.ARCH_GCN}.get(arch, _lib.ARCH_TRANSFORMER)
         w.steps, w.c_in, w.feat_dim = self.steps, self.c_in, self.F
         w.hidden = sd["mlp.0.weight"].shape[0]
@@ -155,6 +156,9 @@ class DenoiserEngine:
             w.c_out = self.c_out
             w.head_w0, w.head_b0 = P("final_mlp.0.weight"), P("final_mlp.0.bias")
             w.head_w1, w.head_b1 = P("final_mlp.2.weight"), P("final_mlp.2.bias")
+            if variant == "discrete_rot":                  # the second, 4-wide head
+                w.head_r_w0, w.head_r_b0 = P("final_mlp_rot.0.weight"), P("final_mlp_rot.0.bias")
+                w.head_r_w1, w.head_r_b1 = P("final_mlp_rot.2.weight"), P("final_mlp_rot.2.bias")
         handle = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(self.lib.da_denoiser_create(C.byref(w), self.prec, _lib.stream_ptr(self.device),
@@ -261,14 +265,14 @@ class DenoiserEngine:
             tt, ts = None, int(t)
             nonneg = int(ts - ratio >= 0)
         nz = None if noise is None else _f32(noise, self.device)
-        variant = {"3d": _lib.VARIANT_3D, "discrete": _lib.VARIANT_DISCRETE}.get(self.variant, _lib.VARIANT_2D)
+        variant = {"3d": _lib.VARIANT_3D, "discrete": _lib.VARIANT_DISCRETE, "discrete_rot": _lib.VARIANT_DISCRETE_ROT}.get(self.variant, _lib.VARIANT_2D)
         _lib.check(self.lib.da_ddim_step(C.byref(sched.c), variant, mean_type, x.shape[0], x.shape[1],
                                          _lib.ptr(x), _lib.ptr(model_out), _lib.ptr(tt), ts, int(ratio), nonneg,
                                          float(eta), _lib.ptr(nz), _lib.ptr(out), _lib.stream_ptr(self.device)))
         return out
 
     def ddpm_step(self, sched: Schedule, x, model_out, t, noise=None):
-        if self.variant == "discrete":      # (da_ddpm_step takes neither a denoiser nor a variant: refused here)
+        if self.variant in ("discrete", "discrete_rot"):      # (da_ddpm_step takes neither a denoiser nor a variant: refused here)
             raise _lib.DaError("ddpm_step: the discrete variant has no pose update (d3pm_step)")
         x, model_out = _f32(x, self.device), _f32(model_out, self.device)
         out = torch.empty_like(x)
@@ -421,6 +425,78 @@ class DenoiserEngine:
                                                _lib.ptr(traj), _lib.ptr(x_final), _lib.ptr(ws), ws.numel(), int(bool(use_graph)),
                                                C.byref(o), _lib.stream_ptr(self.device)))
         return traj, x_final
+
+    # ------------------------------------------------------------------ discrete position + rotation variant
+    def set_features_rot(self, plan, feats4):
+        """Stage the FOUR feature images of a Batch (da_denoiser_set_features_rot): ``feats4`` [4, N, F], image r = the features of the
+        crops rotated by -r quarter turns; [N, F] stages image 0 four times (every rot_acc then selects the same row)."""
+        g, ws = self._workspace(plan)
+        feats4 = _f32(feats4, self.device)
+        if feats4.dim() == 2:
+            feats4 = feats4.unsqueeze(0).expand(4, -1, -1).contiguous()
+        assert feats4.shape == (4, plan.n_real, self.F), (feats4.shape, plan.n_real, self.F)
+        _lib.check(self.lib.da_denoiser_set_features_rot(self.handle, C.byref(g), _lib.ptr(feats4), _lib.ptr(ws), ws.numel(),
+                                                         _lib.stream_ptr(self.device)))
+        return g, ws
+
+    def forward_rot(self, plan, idx, t, feats4=None, rot_acc=None, return_alpha=False):
+        """Eff_GAT_Discrete_ROT.forward_with_feats (da_denoiser_forward_rot): indices [N] -> (logits [N, K], rot_logits [N, 4]) fp32.
+        ``rot_acc`` [N] in {0..3} picks each piece's feature image (``None`` = image 0); ``feats4=None`` reuses the staged images."""
+        if return_alpha:
+            plan.ensure_csr()
+        g, ws = self.set_features_rot(plan, feats4) if feats4 is not None else self._workspace(plan)
+        idx = self._i32(idx)
+        acc = None if rot_acc is None else self._i32(rot_acc)
+        out = torch.empty((plan.n_real, self.c_out), dtype=torch.float32, device=self.device)
+        rout = torch.empty((plan.n_real, 4), dtype=torch.float32, device=self.device)
+        alpha = torch.empty((self.n_layers, plan.n_edges, 8), dtype=torch.float32, device=self.device) if return_alpha else None
+        tt, ts = self._tt(t)
+        _lib.check(self.lib.da_denoiser_forward_rot(self.handle, C.byref(g), _lib.ptr(idx), _lib.ptr(acc), _lib.ptr(tt), ts, _lib.ptr(out),
+                                                    _lib.ptr(rout), _lib.ptr(alpha), 1, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(self.device)))
+        return (out, rout, alpha) if return_alpha else (out, rout)
+
+    def d3pm_rot_step(self, sched: Schedule, x_t, rot_t, logits, rot_logits, t, ratio, **kw):
+        return d3pm_rot_step(sched, x_t, rot_t, logits, rot_logits, t, ratio, **kw)
+
+    def sample_loop_rot(self, plan, sched: Schedule, idx_init, rot_init, feats4, *, ratio=1, max_iters=0, keep_traj=True, use_graph=True,
+                        cold=False, x_fixed=None, noise_x=None, noise_rot=None, generator=None, restage=True):
+        """The position + rotation p_sample_loop in one C call (da_sample_loop_rot; one hipGraph launch when ``use_graph``).  Returns
+        (traj_idx, traj_rot_acc [n_iters, N] int32 or None, idx_final, rot_acc_final [N] int32): engine-owned buffers the next call of
+        the same shape overwrites.  ``x_fixed`` [N]: every step's input indices (``only_rotation``).  Uniforms as in ``sample_loop_idx``:
+        the kernels' generator keyed by the engine's seed tensor, or injected ``noise_x`` [n_iters, N, K] / ``noise_rot`` [n_iters, N, 4]."""
+        total = (sched.steps + ratio - 1) // ratio
+        n_iters = min(max_iters, total) if max_iters and max_iters > 0 else total
+        g, ws = self.set_features_rot(plan, feats4) if restage else self._workspace(plan)
+        n = plan.n_real
+        key = ("rot", n, n_iters, bool(keep_traj), x_fixed is not None)
+        bufs = self._loop_bufs.get(key)
+        if bufs is None:
+            def new(*shape):
+                return torch.empty(shape, dtype=torch.int32, device=self.device)
+            bufs = self._loop_bufs[key] = dict(xi=new(n), ri=new(n), xf=new(n), af=new(n), fixed=new(n) if x_fixed is not None else None,
+                                               tx=new(n_iters, n) if keep_traj else None, ta=new(n_iters, n) if keep_traj else None)
+        bufs["xi"].copy_(idx_init)
+        bufs["ri"].copy_(rot_init)
+        if x_fixed is not None:
+            bufs["fixed"].copy_(x_fixed)
+        self._loop_keep = plan
+        o = _lib.DaD3pmRotOpts()
+        o.cold = int(bool(cold))
+        o.x_fixed = None if x_fixed is None else bufs["fixed"].data_ptr()
+        for name, src, width in (("noise_x", noise_x, self.c_out), ("noise_rot", noise_rot, 4)):
+            if src is not None:
+                nb = self._loop_bufs.get((name,) + key)
+                if nb is None:
+                    nb = self._loop_bufs[(name,) + key] = torch.empty((n_iters, n, width), dtype=torch.float32, device=self.device)
+                nb.copy_(src)
+                setattr(o, name, nb.data_ptr())
+        if noise_x is None or (cold and noise_rot is None):
+            o.seed = self.seed_tensor(generator=generator).data_ptr()
+        _lib.check(self.lib.da_sample_loop_rot(self.handle, C.byref(g), C.byref(sched.c), int(ratio), int(n_iters), _lib.ptr(bufs["xi"]),
+                                               _lib.ptr(bufs["ri"]), _lib.ptr(bufs["tx"]), _lib.ptr(bufs["ta"]), _lib.ptr(bufs["xf"]),
+                                               _lib.ptr(bufs["af"]), _lib.ptr(ws), ws.numel(), int(bool(use_graph)), C.byref(o),
+                                               _lib.stream_ptr(self.device)))
+        return bufs["tx"], bufs["ta"], bufs["xf"], bufs["af"]
 
     # ------------------------------------------------------------------ two-branch loop
     two_branch_min_nodes = 40000       # DA_TWO_BRANCH=auto: the pair loop from this many pieces per Batch
@@ -583,7 +659,7 @@ def d3pm_noise(seed, iteration, n, K, domain="sampling"):
     (``domain="training"``) draws for itself from ``seed`` (int64 [2] device tensor {seed, offset}): [n, K] fp32 in (0, 1]
     (da_d3pm_noise_ex).  The two domains never share a stream."""
     u = torch.empty((n, K), dtype=torch.float32, device=seed.device)
-    dom = {"sampling": _lib.D3PM_DRAW_SAMPLING, "training": _lib.D3PM_DRAW_TRAINING}[domain]
+    dom = {"sampling": _lib.D3PM_DRAW_SAMPLING, "training": _lib.D3PM_DRAW_TRAINING, "sampling_rot": _lib.D3PM_DRAW_SAMPLING_ROT}[domain]
     with torch.cuda.device(seed.device):
         _lib.check(_lib.lib().da_d3pm_noise_ex(_lib.ptr(seed), int(iteration), int(n), int(K), dom, _lib.ptr(u), _lib.stream_ptr(seed.device)))
     return u
@@ -655,6 +731,36 @@ def d3pm_step(sched: Schedule, x_t, logits, t, ratio, noise=None, seed=None, ite
                                            _lib.ptr(nz), _lib.ptr(seed), int(iteration), _lib.ptr(out), _lib.ptr(post),
                                            _lib.stream_ptr(dev)))
     return (out.long(), post) if return_post else out.long()
+
+
+def d3pm_rot_step(sched: Schedule, x_t, rot_t, logits, rot_logits, t, ratio, noise_x=None, noise_rot=None, seed=None, iteration=0,
+                  return_post=False):
+    """p_sample_ddpm of the position + rotation model after the model call (da_d3pm_rot_step, spatial_diffusion_discrete_rot.py:
+    288-330): -> (x_prev, rot_0, rot_prev) int64 [N] (and the two posteriors [N, K], [N, 4] before the Gumbel terms with
+    ``return_post``).  ``noise_x`` [N, K] / ``noise_rot`` [N, 4] uniforms, or ``seed`` (int64 [2] device tensor)."""
+    dev = logits.device
+    if dev.type != "cuda":
+        raise _lib.DaError("d3pm_rot_step needs ROCm tensors (no CPU path in diffassemble_amd)")
+    i32 = lambda x: x.detach().to(device=dev, dtype=torch.int32).contiguous()      # noqa: E731
+    x_t, rot_t, logits, rot_logits = i32(x_t), i32(rot_t), _f32(logits, dev), _f32(rot_logits, dev)
+    n, K = logits.shape
+    if rot_logits.shape != (n, 4) or x_t.shape != (n,) or rot_t.shape != (n,):
+        raise _lib.DaError(f"d3pm_rot_step: logits {tuple(logits.shape)}, rot_logits {tuple(rot_logits.shape)}, x_t {tuple(x_t.shape)}, rot_t {tuple(rot_t.shape)}")
+    xp, r0, rp = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    post = torch.empty_like(logits) if return_post else None
+    rpost = torch.empty_like(rot_logits) if return_post else None
+    nx = None if noise_x is None else _f32(noise_x, dev)
+    nr = None if noise_rot is None else _f32(noise_rot, dev)
+    if torch.is_tensor(t):
+        tt, ts = t.to(device=dev, dtype=torch.int64).contiguous(), 0
+    else:
+        tt, ts = None, int(t)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().da_d3pm_rot_step(C.byref(sched.c), n, K, _lib.ptr(x_t), _lib.ptr(rot_t), _lib.ptr(logits), _lib.ptr(rot_logits),
+                                               _lib.ptr(tt), ts, int(ratio), _lib.ptr(nx), _lib.ptr(nr), _lib.ptr(seed), int(iteration),
+                                               _lib.ptr(xp), _lib.ptr(r0), _lib.ptr(rp), _lib.ptr(post), _lib.ptr(rpost), _lib.stream_ptr(dev)))
+    res = (xp.long(), r0.long(), rp.long())
+    return res + (post, rpost) if return_post else res
 
 
 def linear(x, weight, bias=None, act=_lib.ACT_NONE, residual=None, precision="fp32"):

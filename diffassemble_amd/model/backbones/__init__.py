@@ -4,6 +4,7 @@ the ablation architectures the drivers merely import are placeholders that fail 
 from .efficient_gat import Eff_GAT
 from .efficient_gat_3d import Eff_GAT_3d
 from .efficient_gat_discrete import Eff_GAT_Discrete
+from .efficient_gat_discrete_rotation import Eff_GAT_Discrete_ROT
 from .exophormer_gnn import Exophormer_GNN
 from .gcn import GCN, GCNConv
 from .Transformer_GNN import Transformer_GNN
@@ -21,7 +22,6 @@ def _out_of_scope(name):
 
 
 Dark_TFConv = _out_of_scope("Dark_TFConv")
-Eff_GAT_Discrete_ROT = _out_of_scope("Eff_GAT_Discrete_ROT")
 Eff_GAT_Vist = _out_of_scope("Eff_GAT_Vist")
 
 __all__ = ["Eff_GAT", "Eff_GAT_3d", "Exophormer_GNN", "GCN", "GCNConv", "Transformer_GNN", "TransformerConv",

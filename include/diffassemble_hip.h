@@ -32,7 +32,8 @@ extern "C" {
 
 enum { DA_PREC_F32 = 0, DA_PREC_BF16 = 1 };
 enum { DA_VARIANT_2D = 0, DA_VARIANT_3D = 1,             /* Eff_GAT / Eff_GAT_3d            */
-       DA_VARIANT_DISCRETE = 2 };                        /* Eff_GAT_Discrete (below)        */
+       DA_VARIANT_DISCRETE = 2,                          /* Eff_GAT_Discrete (below)        */
+       DA_VARIANT_DISCRETE_ROT = 3 };                    /* Eff_GAT_Discrete_ROT (below)    */
 enum { DA_ARCH_TRANSFORMER = 0, DA_ARCH_EXOPHORMER = 1, /* GELU between convs / none      */
        DA_ARCH_GCN = 2 };                                /* two GCNConv, GELU after each    */
 enum { DA_MEAN_EPSILON = 0, DA_MEAN_START_X = 1 };       /* spatial_diffusion.py:63-66      */
@@ -93,6 +94,11 @@ int da_build_flags(void);        /* bit 0: EXPERIMENTS build                    
  * denoiser is driven through da_denoiser_forward_idx / da_sample_loop_idx; every entry that takes float poses
  * (da_denoiser_forward, da_sample_loop*, da_ddim_step with this variant) REJECTS it with a da_last_error message and launches
  * nothing (da_ddpm_step takes neither a denoiser nor a variant: the host layer refuses it).  The layout of this struct is unchanged.
+ * DA_VARIANT_DISCRETE_ROT replaces Eff_GAT_Discrete_ROT (backbones/efficient_gat_discrete_rotation.py:19-64): the weights of
+ * DA_VARIANT_DISCRETE plus a second, 4-wide head, head_r_w0 / head_r_b0 = final_mlp_rot.0 [32, D] / [32] and head_r_w1 /
+ * head_r_b1 = final_mlp_rot.2 [4, 32] / [4]; da_denoiser_create checks them.  It is driven through the *_rot entries
+ * (da_denoiser_set_features_rot, da_denoiser_forward_rot, da_sample_loop_rot); the float-pose entries reject it like the
+ * position model, and the *_idx entries reject it with a message that names the rot entries.
  * ------------------------------------------------------------------------------------- */
 typedef struct da_weights {
     int32_t variant;      /* DA_VARIANT_*                                                  */
@@ -117,8 +123,8 @@ typedef struct da_weights {
     const float *virt_emb;                  /* [V, D] or NULL                               */
     const float *head_w0, *head_b0;         /* 2D final_mlp.0 [32, D]; 3D mlp_t.0 [256, D]  */
     const float *head_w1, *head_b1;         /* 2D final_mlp.2 [c_out, 32]; 3D mlp_t.2 [3,256] */
-    const float *head_r_w0, *head_r_b0;     /* 3D mlp_r.0 [256, D] (NULL in 2D)             */
-    const float *head_r_w1, *head_r_b1;     /* 3D mlp_r.2 [3, 256]                          */
+    const float *head_r_w0, *head_r_b0;     /* 3D mlp_r.0 [256, D] (NULL in 2D); discrete rot: final_mlp_rot.0 [32, D] */
+    const float *head_r_w1, *head_r_b1;     /* 3D mlp_r.2 [3, 256]; discrete rot: final_mlp_rot.2 [4, 32]              */
 } da_weights;
 
 /* ---------------------------------------------------------------------------------------
@@ -383,7 +389,8 @@ int da_d3pm_step(const da_schedule *s, int n, int K, const int32_t *x_t, const f
  * u = ((bits >> 8) + 1) 2^-24 in (0, 1].  u [n, K] fp32.                                                                  */
 int da_d3pm_noise(const uint64_t *seed, int iteration, int n, int K, float *u, void *stream);
 /* ... and of a named draw DOMAIN (additive to ABI 19): the reverse step's Gumbel uniforms (da_d3pm_noise) or the training-side
- * noising of da_d3pm_q_sample.  The two use different counter constants, so one seed never gives both the same stream.  */
+ * noising of da_d3pm_q_sample.  The two use different counter constants, so one seed never gives both the same stream.
+ * (A third domain, DA_D3PM_DRAW_SAMPLING_ROT = 2, is declared with the position + rotation model below.)                  */
 enum { DA_D3PM_DRAW_SAMPLING = 0, DA_D3PM_DRAW_TRAINING = 1 };
 int da_d3pm_noise_ex(const uint64_t *seed, int iteration, int n, int K, int domain, float *u, void *stream);
 
@@ -405,6 +412,56 @@ typedef struct da_d3pm_opts {
 int da_sample_loop_idx(da_denoiser *d, const da_graph *g, const da_schedule *s, int inference_ratio, int max_iters,
                        const int32_t *idx_init, int32_t *traj, int32_t *idx_final, void *workspace, size_t workspace_bytes,
                        int use_graph, const da_d3pm_opts *opts, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Discrete position + rotation diffusion (model/spatial_diffusion_discrete_rot.py over
+ * backbones/efficient_gat_discrete_rotation.py; additive to ABI 19).  Besides its position index every piece carries a rotation
+ * in {0, 1, 2, 3} with a second categorical reverse process (rot_K = 4, the same uniform transition), and the sampling loop
+ * accumulates the sampled rotations into rot_acc = (rot_acc + rot) % 4.  The reference rotates the crops by -rot_acc and
+ * re-encodes them every step (:353, :373); rot_acc takes four values per piece, so a Batch has FOUR feature images:
+ *   feats4 [4, n_real, F] fp32, image r = visual_features(rotate_images(cond, -r))
+ * da_denoiser_set_features_rot projects each image through the feature columns of mlp.0 once (the hoist of
+ * da_denoiser_set_features, four times); per step the embedding kernel copies row rot_acc[piece] of those four projections into
+ * the addend of the K = 64 mlp.0 product.  Denoisers / precisions without that hoisted product (da_denoiser_flags bit 3 clear)
+ * are an error in every entry of this section.
+ *   rot_acc  [n_real] int32 in {0..3} (values are taken mod 4), or NULL = image 0 for every piece
+ *   logits [n_real, K], rot_logits [n_real, 4] fp32.  The network does not read the rotation state itself
+ *   (forward_with_feats:87-115): it enters the rotation posterior only, as x_t.                                            */
+int da_denoiser_set_features_rot(da_denoiser *d, const da_graph *g, const float *feats4, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+int da_denoiser_forward_rot(da_denoiser *d, const da_graph *g, const int32_t *idx, const int32_t *rot_acc, const int64_t *t,
+                            int64_t t_scalar, float *logits, float *rot_logits, float *alpha, int alpha_all_layers,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
+/* p_sample_ddpm after the model call (spatial_diffusion_discrete_rot.py:288-330).  The position half is exactly da_d3pm_step
+ * (x_t, logits, noise_x -> x_prev, post_x); the rotation half is the same formula with K = 4 over rot_t / rot_logits / noise_rot
+ * -> rot_prev, post_rot; rot_0 = argmax of the raw rot_logits (lowest index wins).  Without noise buffers the position uniforms
+ * are those of da_d3pm_noise and the rotation uniforms come from the draw domain DA_D3PM_DRAW_SAMPLING_ROT (its own counter
+ * word, flat element r * 4 + k).  rot_0 / rot_prev / post_x / post_rot are nullable.                                        */
+int da_d3pm_rot_step(const da_schedule *s, int n, int K, const int32_t *x_t, const int32_t *rot_t, const float *logits,
+                     const float *rot_logits, const int64_t *t, int64_t t_scalar, int inference_ratio, const float *noise_x,
+                     const float *noise_rot, const uint64_t *seed, int iteration, int32_t *x_prev, int32_t *rot_0,
+                     int32_t *rot_prev, float *post_x, float *post_rot, void *stream);
+enum { DA_D3PM_DRAW_SAMPLING_ROT = 2 };          /* da_d3pm_noise_ex: the rotation half's uniforms, [n, 4] */
+
+/* The whole loop == p_sample_loop (spatial_diffusion_discrete_rot.py:334-375): per step the embedding (with the addend-row
+ * select), the shared body, the two first head layers as one 64-wide product, and ONE tail kernel: both heads, both posteriors,
+ * Gumbel terms, argmax, and the state update  rot = cold ? rot_prev : rot_0,  rot_acc = (rot_acc + rot) % 4.
+ * idx_init / rot_init [n_real] int32 (the reference's two randint draws); traj_idx / traj_rot_acc (nullable) [n_iters, n_real]
+ * int32 receive every step's (index, rot_acc); idx_final / rot_acc_final (nullable) the last.  hipGraph cache and capture rules
+ * of da_sample_loop_idx.                                                                                                    */
+typedef struct da_d3pm_rot_opts {
+    int32_t cold;             /* cold_diffusion: the rotation state follows rot_prev (sampled), else rot_0 (argmax)       */
+    int32_t reserved0;
+    const int32_t *x_fixed;   /* [n_real] or NULL; only_rotation: every step's INPUT index (the returned one is the sample) */
+    const float *noise_x;     /* [n_iters, n_real, K] or NULL                                                              */
+    const float *noise_rot;   /* [n_iters, n_real, 4] or NULL (read only when cold != 0)                                   */
+    const uint64_t *seed;     /* device {seed, offset}; required where a noise buffer is missing                           */
+} da_d3pm_rot_opts;
+int da_sample_loop_rot(da_denoiser *d, const da_graph *g, const da_schedule *s, int inference_ratio, int max_iters,
+                       const int32_t *idx_init, const int32_t *rot_init, int32_t *traj_idx, int32_t *traj_rot_acc,
+                       int32_t *idx_final, int32_t *rot_acc_final, void *workspace, size_t workspace_bytes, int use_graph,
+                       const da_d3pm_rot_opts *opts, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Measurement aid (no reference counterpart: the reference has no profiler hooks).
