@@ -108,6 +108,7 @@ struct da_denoiser {
     void *conv0c_wqs = nullptr;                             // conv0c_wd's per-head fragments (see ConvW::wqs)
     bool attn_qsf = false;            // disable_folds bit 64 was clear when this denoiser was created: the wqs images exist, hidden layers of large complete
                                       // graphs are projected by their attention kernel (a later da_config_set changes neither)
+    bool attn_x_fm = false;           // ... and disable_folds bit 128 (DA_FOLD_X_FM) was clear too: two such layers in a row hand their rows over fragment-major
     float *conv0c_bd = nullptr;
     bool q_prescaled = false;
     // ... and the LAST conv's value / skip projections are folded with final_mlp.0 (its consumer, linear up to
@@ -190,8 +191,10 @@ static Workspace carve(const da_denoiser *d, const da_graph *g, void *base) {
     w.combined = take(np * d->D * s);
     const bool gcn = d->arch == DA_ARCH_GCN;           // (the GCN reads none of the attention buffers: xa / xb / z / combined only)
     w.qkvs = take(gcn ? 0 : np * 4 * (size_t)hcmax * s);
-    w.xa = take(np * 256 * s);
-    w.xb = take(np * 256 * s);
+    // (hidden layers' rows; fragment-major between two layers projected by their attention kernel, run_forward: n_pad rows of padded slots then)
+    const size_t nx = (g->dense || g->hybrid) && (size_t)g->n_pad > np ? (size_t)g->n_pad : np;
+    w.xa = take(nx * 256 * s);
+    w.xb = take(nx * 256 * s);
     w.z = take(np * d->D * s);
     w.hh = take(nrp * d->head_hidden * s);
     const bool disc = d->variant == DA_VARIANT_DISCRETE;
@@ -366,6 +369,23 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
     // (a-4..a-6) graph transformer: fused Q|K|V|skip projection + attention per layer
     const void *xin = fused ? w.h : w.combined;
     int ldx = fused ? d->hidden : D;
+    // Whether layer l, fed rows of length ldx_in, is projected by its own attention kernel (k_attn_res<.., 64>: no projection kernel, K | V never
+    // leave the CU).  ONE predicate, asked twice: for the layer at hand, and one layer ahead -- two such layers in a row hand their rows over
+    // fragment-major (x_fm below), and the layer that writes them has to know what its reader will be.
+    auto layer_qsf = [&](int l, int ldx_in) -> bool {
+        if (l < 0 || l >= d->n_layers - 1 || d->arch == DA_ARCH_GCN) return false;          // (the last layer has its own kernels)
+        const ConvW &c = d->conv[l];
+        const int din = (fused && l == 0) ? d->hidden : c.din;
+        const void *wqs = (fused && l == 0) ? d->conv0c_wqs : c.wqs;
+        const bool virt0 = fused && l == 0 && n > nr, al = alpha && alpha_all;
+        if (al || !w.dq || !dense_ok(g, d->heads, c.C)) return false;
+#ifdef DA_EXPERIMENTS
+        if (g->dense && !g->hybrid && n == nr && conv_fused_applicable(prec, d->heads, c.C, din, g->max_graph_nodes, c.hc)) return false;
+#endif
+        return !g->hybrid && !virt0 && n == nr && wqs && ldx_in == din &&
+               attn_qsf_applicable(prec, d->heads, c.C, din, g->n_graphs, g->max_graph_nodes, g->n_pad, d->q_prescaled);
+    };
+    bool x_fm = false;          // xin is fragment-major over the padded slots (written so by the previous layer's attention kernel)
     if (d->arch == DA_ARCH_GCN) {
         // backbones/gcn.py:16-22, gelu(conv1(gelu(conv0(x)))), reassociated so that both aggregations run 256 wide:
         // conv 0 projects first (A_hat (X W0^T)), conv 1 aggregates first ((A_hat H) W1^T); the residual `feats + combined_feats`
@@ -474,8 +494,12 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
             // Hidden layers of large complete graphs: the resident attention kernel (k_attn_res<.., 64>) does the layer's projection in its own
             // prologue -- no projection kernel, K | V never leave the CU
             const void *wqs = (fused && l == 0) ? d->conv0c_wqs : c.wqs;
-            const bool qsf = !last && !g->hybrid && !resid && !virt0 && n == nr && wqs && ldx == c.din &&
-                             attn_qsf_applicable(prec, d->heads, c.C, c.din, g->n_graphs, g->max_graph_nodes, g->n_pad, d->q_prescaled);
+            const bool qsf = !resid && layer_qsf(l, ldx);
+            // ... and hands its rows to the next layer in MFMA operand order where that one is projected the same way (disable_folds bit 128 clear
+            // at creation): its prologue then reads 1 KB-contiguous fragments instead of 32-byte pieces of 64 rows.  Private between the two launches;
+            // the last hidden layer's rows stay row-major (the last layer's projection and the tail kernel read them)
+            const bool out_fm = qsf && d->attn_x_fm && layer_qsf(l + 1, c.hc);
+            DA_REQUIRE(!x_fm || qsf, "da_denoiser_forward: layer %d was handed fragment-major rows it does not take", l);
             if (qsf) rc = 0; else
             rc = timed(d, DA_PROF_LINEAR_QKVS, st, [&] {
                 return launch_gemm_mfma(prec, nproj, c.din, 4 * c.hc, xin, ldx, wdense, bdense, DA_ACT_NONE, nullptr, nullptr, 0, &qs, st, 0,
@@ -487,7 +511,7 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
             if (rc == 0) {
                 DenseLayout L;
                 L.Q = w.dq; L.K = w.dk; L.Vt = w.dvt; L.S = w.dskip; L.n_pad = g->n_pad; L.q_prescaled = d->q_prescaled;
-                if (qsf) { L.x = xin; L.ldx = ldx; L.kin = c.din; L.wqs = wqs; L.bias = bdense; }
+                if (qsf) { L.x = xin; L.ldx = ldx; L.kin = c.din; L.wqs = wqs; L.bias = bdense; L.x_fm = x_fm; L.out_fm = out_fm; }
                 if (g->hybrid) {
                     // sparse-but-heavy graphs: masked MFMA attention over the regular edges (partial softmax
                     // state), then the remaining edges + normalisation + skip / activation on the CSR side
@@ -551,9 +575,10 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
                     return launch_attn_dense(prec, L, d->heads, c.C, g->n_graphs, g->max_graph_nodes, g->graph_ptr,
                                              g->pad_ptr, g->dense == 2, resid, act, dst, st); });
                 if (rc > 0) return rc;
-                if (rc == 0) { xin = dst; ldx = c.hc; continue; }
+                if (rc == 0) { xin = dst; ldx = c.hc; x_fm = out_fm; continue; }
             }
         }
+        DA_REQUIRE(!x_fm, "da_denoiser_forward: layer %d was handed fragment-major rows it does not take", l);
         if ((rc = timed(d, DA_PROF_LINEAR_QKVS, st, [&] {
                  return linear(prec, nproj, c.din, 4 * c.hc, xin, ldx, c.w, c.b, DA_ACT_NONE, nullptr, w.qkvs, 4 * c.hc, st); }))) return rc;
         if (virt0 && (rc = launch_scatter_virtual(prec, n - nr, d->V, d->heads, c.C, d->virt_qkvs, nr, nullptr, 0, nullptr, nullptr,
@@ -771,6 +796,7 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
     };
     // per-head Q / skip fragments of a hidden layer's dense-path projection (bf16, 32-wide heads, K = 128 / 256); nullptr otherwise
     d->attn_qsf = attn_qsf_enabled();
+    d->attn_x_fm = d->attn_qsf && !(cfg().disable_folds & DA_FOLD_X_FM);
     auto pack_qs = [&](const void *wsrc, int K, int hc, int C) -> void * {
         if (!d->attn_qsf) return nullptr;
         if (precision != DA_PREC_BF16 || C != 32 || H != 8 || (K != 128 && K != 256) || !wsrc || mfma_disabled()) return nullptr;
@@ -1533,6 +1559,9 @@ int da_conv_dense_ex(int prec, const da_graph *g, int heads, int C, int Din, con
     const bool qsf = attn_qsf_enabled() && !folded && !residual && !g->hybrid && g->n_nodes == g->n_real && b && w_qs_bytes(heads, Din) <= 2 * hb &&
                      attn_qsf_applicable(prec, heads, C, Din, g->n_graphs, g->max_graph_nodes, g->n_pad, (flags & DA_CONV_Q_PRESCALED) ? 1 : 0);
     void *wq_img = base + hb;                        // (the K | V regions of the scratch: K | V stay in the CU)
+    // fragment-major rows are a layout of THAT kernel's prologue and epilogue: no other path reads or writes it
+    DA_REQUIRE(qsf || !(flags & DA_CONV_X_FM), "da_conv_dense_ex: DA_CONV_X_FM on a call that does not take the projection in the attention kernel");
+    DA_REQUIRE(qsf || !(flags & DA_CONV_OUT_FM), "da_conv_dense_ex: DA_CONV_OUT_FM on a call that does not take the projection in the attention kernel");
     int rc = 0;
     if (qsf) {
         if ((rc = pack_w_qs(heads, Din, (int)hc, w, wq_img, st))) return rc;
@@ -1541,7 +1570,7 @@ int da_conv_dense_ex(int prec, const da_graph *g, int heads, int C, int Din, con
     DA_REQUIRE(rc == 0, "da_conv_dense_ex: projection shape (Din=%d, Nout=%d) not supported by the MFMA kernels", Din, nout);
     DenseLayout L;
     L.Q = qs.Q; L.K = qs.K; L.Vt = qs.Vt; L.S = qs.S; L.n_pad = g->n_pad; L.q_prescaled = (flags & DA_CONV_Q_PRESCALED) ? 1 : 0;
-    if (qsf) { L.x = x; L.ldx = Din; L.kin = Din; L.wqs = wq_img; L.bias = b; }
+    if (qsf) { L.x = x; L.ldx = Din; L.kin = Din; L.wqs = wq_img; L.bias = b; L.x_fm = (flags & DA_CONV_X_FM) != 0; L.out_fm = (flags & DA_CONV_OUT_FM) != 0; }
     DenseFold fo;
     fo.cv = 32; fo.out = out; fo.n_rows = g->n_real;
     const DenseMask mk = dense_mask_of(g);
@@ -1566,6 +1595,7 @@ int da_debug_counters(int64_t *out, int n, int reset) {
     out[DA_DBG_OPT_MASKED_GEN_WORKGROUPS] = (int64_t)a[2];
     out[DA_DBG_RES_LAUNCHES] = (int64_t)da::attn_res_launches(reset);
     out[DA_DBG_RES_PROJ_LAUNCHES] = (int64_t)da::attn_res_qsf_launches(reset);
+    out[DA_DBG_RES_FM_LAUNCHES] = (int64_t)da::attn_res_fm_launches(reset);
     out[DA_DBG_VIRT_IN_LAUNCH] = (int64_t)da::attn_virt_launches(reset);
     return 0;
 }

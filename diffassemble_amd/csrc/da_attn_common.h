@@ -55,6 +55,11 @@ struct AttnDenseParams {
     int ldx, kin;                   // kin = reduction length (128 / 256)
     const void *wqs;
     const float *bias_q, *bias_k, *bias_v, *bias_s;   // [H * 32] each
+    // k_attn_res<.., 64>, rows in MFMA operand order ("fragment-major", FM) over the padded slots: 16-byte piece [16 s + 8 half .. + 7] of slot row r
+    // lives at ((r >> 5) * KS + s) * 1024 + (half * 32 + (r & 31)) * 16, KS = row length / 16 -- one (32-row slab, k-step) is 1 KB, lane (i, half)'s
+    // B fragment of k-step s the 16 bytes at lane * 16 inside it.  x_fm: x is stored so (ldx unused); out_fm: out is written so, every row of a
+    // slab the graph owns (rows >= n_g of its last slab as zeros), for the next layer's x_fm launch
+    int x_fm = 0, out_fm = 0;
 };
 
 template <typename T, int C, int CV = C, int BK = 0> struct Cfg {

@@ -862,6 +862,8 @@ int launch_attn_dense(int prec, const DenseLayout &L, int heads, int C, int n_gr
     p.graph_ptr = graph_ptr; p.pad_ptr = pad_ptr; p.n_pad = L.n_pad; p.H = heads; p.n_graphs = n_graphs;
     p.nqt = 0; p.max_nodes = max_graph_nodes; p.act = act; p.nodiag = nodiag;
     p.x = L.x; p.ldx = L.ldx; p.kin = L.kin; p.wqs = L.wqs;
+    DA_REQUIRE(L.x || !(L.x_fm || L.out_fm), "launch_attn_dense: fragment-major rows without the projection in the attention kernel");
+    p.x_fm = L.x_fm ? 1 : 0; p.out_fm = L.out_fm ? 1 : 0;
     p.bias_q = L.bias; p.bias_k = L.bias ? L.bias + heads * C : nullptr; p.bias_v = L.bias ? L.bias + 2 * heads * C : nullptr; p.bias_s = L.bias ? L.bias + 3 * heads * C : nullptr;
     p.fast = L.q_prescaled ? 1 : 0;
     if (DA_XENV("DA_ATTN_NO_FAST", 0)) p.fast = 0;
@@ -879,7 +881,6 @@ int launch_attn_dense(int prec, const DenseLayout &L, int heads, int C, int n_gr
     p.v_part = virt ? mk->v_part : nullptr; p.v_cnt = virt ? mk->v_cnt : nullptr;
     if (mk && mk->v_taken) *mk->v_taken = 0;
     { const char *e = DA_XENV_LIVE("DA_ATTN_DEBUG"); p.debug = e ? atoi(e) : 0; }
-    if (p.x && DA_XENV("DA_QSF_FAKE_FM", 0)) p.debug = 77;
     { const int fg = DA_XENV("DA_ATTN_FORCE_GEN", 0) ? 1 : 0; p.force_gen = fg; if (fg) p.fast = p.fast ? 2 : 0; }
     { const char *e = DA_XENV_LIVE("DA_ATTN_PROF_PTR"); p.prof = e ? (unsigned long long *)strtoull(e, nullptr, 0) : nullptr; }
     if (n_graphs <= 0 || max_graph_nodes <= 0) return 0;

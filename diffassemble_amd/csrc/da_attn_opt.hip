@@ -933,7 +933,10 @@ __global__ __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : ((NWV > 5 || (XV & 8)) ? 
     // bit 6 (64) = THE LAYER'S PROJECTION IN THE PROLOGUE (round 6; + bit 7 (128): reduction length 128 instead of 256): no projection kernel runs in
     // front of this one.  The workgroup of a (graph, head) projects that head's Q | K | V | skip columns of ITS graph itself, on the matrix pipe,
     // while nothing else is going on in the CU: wave w takes the 32-node slabs w and w + 16.  x rows come from global memory in operand shape
-    // (lane (node, half), k-step s: x[node][16 s + 8 half .. + 7]), the head's four 32 x KIN weight blocks are A operands out of LDS (pack_w_qs
+    // (lane (node, half), k-step s: x[node][16 s + 8 half .. + 7]) -- from row-major x (the first conv's input) as 32-byte pieces of 64 rows per request,
+    // from FRAGMENT-MAJOR x (p.x_fm: written so by the previous layer's epilogue, p.out_fm, over the padded slots; AttnDenseParams) as one contiguous
+    // KB per request: the eight heads' workgroups of a graph all read all of its rows, and the request shape is what the prologue's time went into
+    // (profiles/r11/NOTES.md).  The head's four 32 x KIN weight blocks are A operands out of LDS (pack_w_qs
     // image: MFMA row a = channel pi(a), bits 2 and 3 swapped, so registers 8 t .. 8 t + 7 of a lane are the 16-byte chunk 2 t + half of its
     // node's row -- in every layout that follows).  The Q and skip weights sit in the last stages of the image, which slabs >= 16 fill last (graphs whose
     // image is too short for that -- below 12 stages at a reduction of 256, 10 at 128 -- leave room for them BEHIND the image instead): rows to p.Q / p.S in the
@@ -1081,13 +1084,15 @@ __global__ __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : ((NWV > 5 || (XV & 8)) ? 
     static_assert(!PROG || CF::NCH == 2, "progressive landing: two Q fragments per lane");
     // ---- QSF: the projection prologue (see the header of the kernel)
     [[maybe_unused]] u32x4 xq[KS];          // a slab's x rows, every k-step (one memory round trip per slab)
-    [[maybe_unused]] const int xstep = p.debug == 77 ? 1024 : 32;          // bytes between a lane's fragments of consecutive k-steps
+    // p.x_fm: x is stored fragment-major over the padded slots by its producer (the previous layer's epilogue below; AttnDenseParams::x_fm) --
+    // slab sl's k-step s is ONE contiguous KB, this lane's fragment the 16 bytes at lane * 16 inside it; row-major x (the first conv's input,
+    // da_conv_dense_ex): 32-byte pieces of 64 different rows per request
+    [[maybe_unused]] const int xstep = p.x_fm ? 1024 : 32;          // bytes between a lane's fragments of consecutive k-steps
     [[maybe_unused]] auto x_row = [&](int sl) {
+        // (FM: no clamp -- rows behind the graph are read as stored; project_kv keeps them out of the image)
+        if (p.x_fm) return (const unsigned char *)p.x + ((size_t)((pad0 >> 5) + sl) * KS) * 1024 + lane * 16;
         const int nd = max(min(sl * 32 + i, n_g - 1), 0);          // (rows behind the graph repeat its last row: finite K / V rows, never stored Q / skip rows)
-        const unsigned char *row = (const unsigned char *)p.x + ((size_t)(node0 + nd) * (size_t)p.ldx + 8 * half) * 2;
-        // (p.debug == 77, timing only, WRONG results: the same bytes as 1 KB-contiguous loads, as if x were stored fragment-major)
-        if (p.debug == 77) row = (const unsigned char *)p.x + ((size_t)(node0 + max(min(sl * 32, n_g - 32), 0)) * (size_t)p.ldx) * 2 + lane * 16;
-        return row;
+        return (const unsigned char *)p.x + ((size_t)(node0 + nd) * (size_t)p.ldx + 8 * half) * 2;
     };
     [[maybe_unused]] auto x_issue = [&](int sl) {
         const unsigned char *row = x_row(sl);
@@ -1156,13 +1161,17 @@ __global__ __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : ((NWV > 5 || (XV & 8)) ? 
     [[maybe_unused]] auto project_kv = [&](auto rl, int sl, const unsigned char *nxt = nullptr) {
         const int rt = (sl & 1) * 32 + i;          // row inside the 64-key stage
         unsigned char *st_ = smem + (size_t)(sl >> 1) * STAGE + (size_t)rt * 64;
+        // rows behind the graph (the last slab's): zeros in the image, whatever x held there -- their scores are masked, but a V row takes part in the
+        // PV product with weight 0, and 0 x NaN is NaN (row-major x repeats the last row there; fragment-major x is read as stored)
+        const bool live = sl * 32 + i < n_g;          // (a lane mask in scalar registers)
+        auto keep_live = [&](u32x4 c_) { return live ? c_ : (u32x4){0u, 0u, 0u, 0u}; };
         f32x16 a;
         chain1(NoReload(), wimg, a);
 #pragma unroll
-        for (int t = 0; t < 2; ++t) *(u32x4 *)(st_ + (((2 * t + half) ^ KG::f(rt)) << 4)) = chunk_of(a, 1, t);
+        for (int t = 0; t < 2; ++t) *(u32x4 *)(st_ + (((2 * t + half) ^ KG::f(rt)) << 4)) = keep_live(chunk_of(a, 1, t));
         chain1(rl, wimg + (size_t)KS * 1024, a, nxt);
 #pragma unroll
-        for (int t = 0; t < 2; ++t) *(u32x4 *)(st_ + KG::KBYTES + ((2 * t + half) << 4)) = chunk_of(a, 2, t);
+        for (int t = 0; t < 2; ++t) *(u32x4 *)(st_ + KG::KBYTES + ((2 * t + half) << 4)) = keep_live(chunk_of(a, 2, t));
     };
     if constexpr (QSF) { if (slab < nslab) x_issue(slab); }          // (a wave without a slab requests nothing: no pending load on its path to the barriers)
     else if constexpr (!PROG) load_q(slab, qf);
@@ -1577,6 +1586,19 @@ __global__ __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : ((NWV > 5 || (XV & 8)) ? 
         if (more) load_q(nxt, qn);
         const float lt = ls + __shfl_xor(ls, 32);
         const float inv = lt > 0.f ? 1.0f / (lt + (gen ? 1e-16f : 0.f)) : 0.f;      // (no epsilon on an un-shifted sum: see the header)
+        // p.out_fm (QSF): the rows go out fragment-major, as the next layer's x_fm prologue reads them.  Head h's 32 channels are k-steps 2 h and 2 h + 1
+        // of the HC-long row; this lane's channels 8 jj + 4 half .. + 3 are bytes 8 half .. + 7 of piece jj & 1 of k-step 2 h + (jj >> 1), i.e. 256 jj
+        // elements behind its jj = 0: per jj the wave's 64 stores cover 512 contiguous bytes (row-major: 64 rows 512 B apart).  The (slab, head) part of
+        // the address is wave-uniform; the lane's part is 8 i + 4 half elements
+        [[maybe_unused]] auto fm_row = [&]() { return (T *)p.out + ((size_t)((pad0 >> 5) + slab) * (size_t)(HC >> 4) + 2 * h) * 512 + (unsigned)(8 * i + 4 * half); };
+        if constexpr (QSF) {
+            // rows behind the graph in a slab it owns: zeros (the consumer reads whole slabs; nothing else ever writes these rows)
+            if (p.out_fm && qidx >= n_g) {
+                T *zrow = fm_row();
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) *(u32x2 *)(zrow + 256 * jj) = (u32x2){0u, 0u};
+            }
+        }
         if (qidx < n_g) {
             const size_t roff = (size_t)(MSK ? my_node : node0 + qidx) * HC + (size_t)h * C + 4 * half;
             u32x2 sk[4], rs[4];
@@ -1585,6 +1607,9 @@ __global__ __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : ((NWV > 5 || (XV & 8)) ? 
                 sk[jj] = *(const u32x2 *)((const T *)p.S + roff + 8 * jj);
                 rs[jj] = p.res ? *(const u32x2 *)((const T *)p.res + roff + 8 * jj) : (u32x2){0u, 0u};
             }
+            T *orow = (T *)p.out + roff;
+            int ostep = 8;          // elements between this lane's four pieces
+            if constexpr (QSF) { if (p.out_fm) { orow = fm_row(); ostep = 256; } }
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
                 // (products rounded on their own, as the ring kernel's are on their way through LDS: no contraction with the skip add)
@@ -1598,7 +1623,7 @@ __global__ __launch_bounds__(64 * NWV, NWV >= 16 ? 1 : ((NWV > 5 || (XV & 8)) ? 
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v4[e] = apply_act(v4[e], p.act);
-                st4((T *)p.out + roff + 8 * jj, v4);
+                st4(orow + jj * ostep, v4);
             }
         }
         if (more) {
@@ -1621,6 +1646,10 @@ long long attn_res_launches(int reset) {
 static long long g_res_qsf_launches = 0;   // [DA_DBG_RES_PROJ_LAUNCHES]: those of them that did their layer's projection themselves (no projection kernel ran)
 long long attn_res_qsf_launches(int reset) {
     return reset ? __atomic_exchange_n(&g_res_qsf_launches, 0ll, __ATOMIC_RELAXED) : __atomic_load_n(&g_res_qsf_launches, __ATOMIC_RELAXED);
+}
+static long long g_res_fm_launches = 0;    // [DA_DBG_RES_FM_LAUNCHES]: those of THEM whose input rows were fragment-major (AttnDenseParams::x_fm)
+long long attn_res_fm_launches(int reset) {
+    return reset ? __atomic_exchange_n(&g_res_fm_launches, 0ll, __ATOMIC_RELAXED) : __atomic_load_n(&g_res_fm_launches, __ATOMIC_RELAXED);
 }
 
 // projection in the prologue (k_attn_res<16, true, true, 64 (+ 128)>): LDS = the K | V tiles + 512 B of words + two weight blocks + 128 bias floats;
@@ -1729,6 +1758,7 @@ int launch_attn_opt(const AttnDenseParams &p, int C, hipStream_t st) {
                     DA_REQUIRE(attn_res_qsf_shape_ok(p.max_nodes, p.n_pad, p.n_graphs, p.kin) && p.wqs && p.bias_q && p.bias_k && p.bias_v && p.bias_s,
                                "k_attn_res: projection in the prologue requested for a shape it does not take");
                     __atomic_fetch_add(&g_res_qsf_launches, 1ll, __ATOMIC_RELAXED);
+                    if (p.x_fm) __atomic_fetch_add(&g_res_fm_launches, 1ll, __ATOMIC_RELAXED);
                     return p.kin == 256 ? launch_res<16, true, true, 64>(p, st) : launch_res<16, true, true, 64 + 128>(p, st);
                 }
 #ifdef DA_EXPERIMENTS

@@ -150,6 +150,8 @@ struct DenseLayout {
     int ldx = 0, kin = 0;
     const void *wqs = nullptr; // pack_w_qs image of the layer's projection weights
     const float *bias = nullptr;   // [4 * H * 32]: Q | K | V | skip
+    // fragment-major rows over the padded slots (AttnDenseParams::x_fm / out_fm; only with x set): x is stored so / out is written so
+    bool x_fm = false, out_fm = false;
 };
 // da_attn_dense.hip / da_attn_opt.hip: whether launch_attn_dense will take the resident kernel's projection-in-the-prologue form for this layer
 bool attn_qsf_applicable(int prec, int heads, int C, int kin, int n_graphs, int max_graph_nodes, int n_pad, int q_prescaled);
@@ -212,6 +214,7 @@ int attn_dense_counters(unsigned long long *out4, int reset);
 long long attn_virt_launches(int reset);     // da_attn_opt.hip: masked hidden-layer launches that carried the virtual rows
 long long attn_res_launches(int reset);      // da_attn_opt.hip: launches of the K / V-resident kernel since the last reset
 long long attn_res_qsf_launches(int reset);  // ... those of them that projected their layer themselves
+long long attn_res_fm_launches(int reset);   // ... and of those, the ones that read their input rows fragment-major
 int attn_dual_counters(unsigned long long *out2, int reset);
 // hybrid mode: the rows the masked kernel does not own (virtual nodes) over their remainder edges
 int launch_attn_csr_cont(int prec, int n_nodes, int n_real, const int32_t *irr_row_ptr, const int32_t *irr_col_src,

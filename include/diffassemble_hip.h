@@ -62,7 +62,10 @@ typedef struct da_config {
                                  /* layer, 4 softmax scale inside Wq, 8 DDIM update inside the head kernel,          */
                                  /* 16 one-kernel tail, 32 virtual rows on a side stream / inside the masked         */
                                  /* attention's launch (hybrid graphs), 64 a hidden layer's Q|K|V|skip projection in */
-                                 /* the prologue of its K/V-resident attention kernel (no projection kernel)         */
+                                 /* the prologue of its K/V-resident attention kernel (no projection kernel),        */
+                                 /* 128 such layers handing their rows to the next one in MFMA operand order         */
+                                 /* (fragment-major over the padded slots; needs bit 64 clear; fixed per denoiser    */
+                                 /* at creation, like bit 64)                                                        */
     int32_t attn_level;          /* DA_ATTN_LEVEL: 0 = the general dense kernel only, 1 = + the optimistic ring      */
                                  /* kernels, 2 = + the K/V-resident hidden-layer kernel (default)                    */
     int32_t xpanel;              /* DA_ENABLE_XPANEL: -1 = row-panel projections for large Batches (largest graph    */
@@ -530,6 +533,14 @@ int da_conv_dense(int prec, const da_graph *g, int heads, int C, int Din, const 
  * beyond da_conv_dense's (Transformer_GNN.py:32,38): kernel-level test entry for those paths.                          */
 #define DA_CONV_Q_PRESCALED 1
 #define DA_CONV_FOLDED_V32 2
+/* Where the call takes the projection in the attention kernel's prologue (large complete graphs, disable_folds bit 64 clear), the
+ * layer's rows in the MFMA operand order two such layers hand them over in inside the denoiser (disable_folds bit 128 clear):
+ * 16-byte piece [16 s + 8 half .. + 7] of PADDED slot row r (plan->row_map) of a [n_pad][L] bf16 buffer at byte
+ * ((r >> 5) * (L / 16) + s) * 1024 + (half * 32 + (r & 31)) * 16.  DA_CONV_X_FM: x is such a buffer (L = Din; rows behind a
+ * graph inside its last 32-row slab may hold anything); DA_CONV_OUT_FM: out is written so (L = H * C; those rows as zeros, slabs
+ * behind the graph's last are not touched).  Any other call with one of the two flags is an error.                              */
+#define DA_CONV_X_FM 4
+#define DA_CONV_OUT_FM 8
 int da_conv_dense_ex(int prec, const da_graph *g, int heads, int C, int Din, const void *x, const void *w,
                      const float *b, const void *residual, int act, void *out, void *scratch, int flags,
                      void *stream);
@@ -546,6 +557,8 @@ enum {
     DA_DBG_VIRT_IN_LAUNCH = 5,             /* masked hidden-layer launches that carried the exophormer's virtual rows */
     DA_DBG_RES_PROJ_LAUNCHES = 6,          /* k_attn_res launches that projected Q | K | V | skip of their layer in   */
                                            /* their own prologue (disable_folds bit 64 clear): no projection kernel   */
+    DA_DBG_RES_FM_LAUNCHES = 7,            /* ... and of those, the launches that read their input rows fragment-major */
+                                           /* (disable_folds bit 128 clear; DA_CONV_X_FM)                             */
     DA_DBG_NCOUNTERS = 8
 };
 int da_debug_counters(int64_t *out /* host [n] */, int n, int reset);
