@@ -25,7 +25,7 @@ CONV_X_FM, CONV_OUT_FM = 4, 8          # da_conv_dense_ex: x is / out is written
 FOLD_ATTN_PROJ, FOLD_X_FM = 64, 128    # da_config.disable_folds: set = keep the projection kernel / keep the hidden layers' rows row-major between them
 TRAIN_MMA_FP32, TRAIN_MMA_BF16 = 0, 1
 TRAIN_BWD_ALL, TRAIN_BWD_EARLY, TRAIN_BWD_LATE = 0, 1, 2
-D3PM_DRAW_SAMPLING, D3PM_DRAW_TRAINING, D3PM_DRAW_SAMPLING_ROT = 0, 1, 2
+D3PM_DRAW_SAMPLING, D3PM_DRAW_TRAINING, D3PM_DRAW_SAMPLING_ROT, D3PM_DRAW_TRAINING_ROT = 0, 1, 2, 3
 D3PM_LOSS = {"vb": 0, "cross_entropy": 1, "hybrid": 2}
 DBG_COUNTERS = ("opt_gen_workgroups", "dense_fast_exits", "dual_gen_slabs", "opt_masked_gen_workgroups")          # fallback events (indices 0 .. 3)
 DBG_LAUNCH_COUNTERS = {"resident_launches": 4, "virtual_rows_in_launch": 5,           # which kernel took a layer (DA_DBG_RES_LAUNCHES, DA_DBG_VIRT_IN_LAUNCH,
@@ -213,6 +213,12 @@ PROTOTYPES = {
     "da_d3pm_loss": (C.c_int, [C.POINTER(DaSchedule), C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "da_train_forward_idx": (C.c_int, [C.POINTER(DaWeights), C.POINTER(DaGraph), _fp, _fp, _fp, _fp, _fp, C.c_size_t, C.c_int, _fp]),
     "da_train_backward_idx": (C.c_int, [C.POINTER(DaWeights), C.POINTER(DaWeights), C.POINTER(DaGraph), _fp, _fp, _fp, _fp,
+                                        _fp, C.c_size_t, C.c_int, C.c_int, _fp]),
+    "da_d3pm_q_sample_rot": (C.c_int, [C.POINTER(DaSchedule), C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp]),
+    "da_d3pm_rot_loss": (C.c_int, [C.POINTER(DaSchedule), C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                   _fp, _fp, _fp]),
+    "da_train_forward_rot": (C.c_int, [C.POINTER(DaWeights), C.POINTER(DaGraph), _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, C.c_int, _fp]),
+    "da_train_backward_rot": (C.c_int, [C.POINTER(DaWeights), C.POINTER(DaWeights), C.POINTER(DaGraph), _fp, _fp, _fp, _fp, _fp,
                                         _fp, C.c_size_t, C.c_int, C.c_int, _fp]),
     "da_sample_loop_idx": (C.c_int, [_fp, C.POINTER(DaGraph), C.POINTER(DaSchedule), C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t,
                                      C.c_int, C.POINTER(DaD3pmOpts), _fp]),

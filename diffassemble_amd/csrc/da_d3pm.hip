@@ -233,8 +233,8 @@ int da_d3pm_noise(const uint64_t *seed, int iteration, int n, int K, float *u, v
 
 int da_d3pm_noise_ex(const uint64_t *seed, int iteration, int n, int K, int domain, float *u, void *stream) {
     DA_REQUIRE(seed && u && n >= 0 && K >= 1, "da_d3pm_noise: bad argument");
-    DA_REQUIRE(domain == DA_D3PM_DRAW_SAMPLING || domain == DA_D3PM_DRAW_TRAINING || domain == DA_D3PM_DRAW_SAMPLING_ROT,
-               "da_d3pm_noise: unknown draw domain %d", domain);
+    DA_REQUIRE(domain == DA_D3PM_DRAW_SAMPLING || domain == DA_D3PM_DRAW_TRAINING || domain == DA_D3PM_DRAW_SAMPLING_ROT ||
+                   domain == DA_D3PM_DRAW_TRAINING_ROT, "da_d3pm_noise: unknown draw domain %d", domain);
     const size_t total = (size_t)n * K;
     if (!total) return 0;
     k_d3pm_noise<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(seed, (uint32_t)iteration, d3pm_domain_word(domain), total, u);

@@ -271,8 +271,10 @@ struct D3pmRows {
 // (da_d3pm_train.hip) use different words, so one seed never gives the two the same stream.
 constexpr uint32_t D3PM_WORD_SAMPLING = 0xD3B07384u, D3PM_WORD_TRAINING = 0x51ED270Bu;
 constexpr uint32_t D3PM_WORD_SAMPLING_ROT = 0x2A65C0F1u;      // the rotation half of the position + rotation model (da_d3pm_rot.hip)
+constexpr uint32_t D3PM_WORD_TRAINING_ROT = 0x7C3A91E5u;      // the rotation half of the training-side noising (da_d3pm_rot_train.hip)
 inline uint32_t d3pm_domain_word(int domain) {
-    return domain == DA_D3PM_DRAW_TRAINING ? D3PM_WORD_TRAINING : domain == DA_D3PM_DRAW_SAMPLING_ROT ? D3PM_WORD_SAMPLING_ROT : D3PM_WORD_SAMPLING;
+    return domain == DA_D3PM_DRAW_TRAINING ? D3PM_WORD_TRAINING : domain == DA_D3PM_DRAW_SAMPLING_ROT ? D3PM_WORD_SAMPLING_ROT :
+           domain == DA_D3PM_DRAW_TRAINING_ROT ? D3PM_WORD_TRAINING_ROT : D3PM_WORD_SAMPLING;
 }
 __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t ctr, uint32_t iteration, uint32_t word = D3PM_WORD_SAMPLING) {
     uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = iteration, c3 = word;

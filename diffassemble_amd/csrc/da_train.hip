@@ -894,8 +894,9 @@ struct Dims {
     int din[DA_MAX_LAYERS], C[DA_MAX_LAYERS], hc[DA_MAX_LAYERS];
     bool gelu_between;
     bool v3d;                  // DA_VARIANT_3D (efficient_gat_3d.py): LeakyReLU mlp, two pose heads behind one 512-wide hidden product
-    int hh;                    // width of the head's hidden layer: 32 (final_mlp.0), 3D: 512 (mlp_t.0 | mlp_r.0)
+    int hh;                    // width of the head's hidden layer: 32 (final_mlp.0), 3D: 512 (mlp_t.0 | mlp_r.0), discrete rot: 64 (final_mlp.0 | final_mlp_rot.0)
     bool disc;                 // DA_VARIANT_DISCRETE (efficient_gat_discrete.py): embedding lookup where the pose MLP was, K-wide logits head (c_out = K)
+    bool rot;                  // DA_VARIANT_DISCRETE_ROT (efficient_gat_discrete_rotation.py): disc plus a 4-wide rotation head; final_mlp.0 | final_mlp_rot.0 one 64-wide product
     bool gcn;                  // DA_ARCH_GCN (backbones/gcn.py): two GCNConv, aggregation by da_gcn.hip, no attention
     bool dense;                // complete graphs: grouped-GEMM attention (da_train_dense.hip)
     bool hybrid;               // hybrid graphs: masked grouped GEMMs + CSR remainder (da_train_dense.hip)
@@ -910,15 +911,17 @@ struct Dims {
 static int dims_of(const da_weights *w, const da_graph *g, Dims &d, int mma = DA_TRAIN_MMA_FP32) {
     d.bfc = mma == DA_TRAIN_MMA_BF16;
     DA_REQUIRE(w && g, "training: null argument");
-    DA_REQUIRE(w->variant == DA_VARIANT_2D || w->variant == DA_VARIANT_3D || w->variant == DA_VARIANT_DISCRETE, "training: unknown variant %d", w->variant);
+    DA_REQUIRE(w->variant == DA_VARIANT_2D || w->variant == DA_VARIANT_3D || w->variant == DA_VARIANT_DISCRETE || w->variant == DA_VARIANT_DISCRETE_ROT,
+               "training: unknown variant %d", w->variant);
     d.v3d = w->variant == DA_VARIANT_3D;
-    d.disc = w->variant == DA_VARIANT_DISCRETE;
+    d.rot = w->variant == DA_VARIANT_DISCRETE_ROT;
+    d.disc = w->variant == DA_VARIANT_DISCRETE || d.rot;
     if (d.disc) {
         DA_REQUIRE(w->arch == DA_ARCH_TRANSFORMER, "training (discrete variant): the transformer architecture only, as in inference");
         DA_REQUIRE(w->c_out >= 2 && w->c_out <= 1024, "training (discrete variant): K = c_out = %d outside [2, 1024]", w->c_out);
         DA_REQUIRE(w->c_in == 1 && w->pos_w1, "training (discrete variant): c_in must be 1 and pos_w1 = pos_mlp.weight [K, 32]");
     }
-    d.hh = d.v3d ? 512 : 32;
+    d.hh = d.v3d ? 512 : (d.rot ? 64 : 32);
     DA_REQUIRE(!d.v3d || w->c_in == 7, "training (3D): c_in must be 7 (quaternion wxyz | translation), not %d", w->c_in);
     DA_REQUIRE(w->c_in >= 1 && w->c_in <= 8, "training: c_in %d outside 1 .. 8", w->c_in);
     d.gcn = w->arch == DA_ARCH_GCN;
@@ -1033,6 +1036,8 @@ static TrainWs carve_train(const Dims &d, void *base) {
         w.wt_head_r1 = take((size_t)3 * 256);
         w.pre6 = take(nr * 6);
         w.dpre6 = take(nr * 6);
+    } else if (d.rot) {
+        w.wt_head_r1 = take((size_t)4 * 32);
     }
     w.total = off;
     return w;
@@ -1044,6 +1049,12 @@ static int check_fused(const da_weights *w, const Dims &d, const char *what) {
         DA_REQUIRE(w->head_r_w0 && w->head_r_b0 && w->head_r_w1 && w->head_r_b1, "%s: 3D head_r_* pointers (mlp_r) missing", what);
         DA_REQUIRE(w->head_r_w0 == w->head_w0 + (size_t)256 * d.D && w->head_r_b0 == w->head_b0 + 256,
                    "%s: the 3D heads need mlp_t.0 | mlp_r.0 contiguous in that order, weights and biases (flat parameter buffer)", what);
+    }
+    if (d.rot) {
+        DA_REQUIRE(w->head_w0 && w->head_b0 && w->head_w1 && w->head_b1, "%s: discrete rot head pointers (final_mlp) missing", what);
+        DA_REQUIRE(w->head_r_w0 && w->head_r_b0 && w->head_r_w1 && w->head_r_b1, "%s: discrete rot head_r_* pointers (final_mlp_rot) missing", what);
+        DA_REQUIRE(w->head_r_w0 == w->head_w0 + (size_t)32 * d.D && w->head_r_b0 == w->head_b0 + 32,
+                   "%s: the two heads need final_mlp.0 | final_mlp_rot.0 contiguous in that order, weights and biases (flat parameter buffer)", what);
     }
     for (int l = 0; l < d.L && d.gcn; ++l)
         DA_REQUIRE(w->conv_wq[l] && w->conv_bq[l], "%s: gcn conv %d pointers (lin.weight, bias) missing", what, l);
@@ -1080,6 +1091,7 @@ static int weight_prep(const da_weights *w, const Dims &d, TrainWs &ws, hipStrea
         add(w->head_r_w1, ws.wt_head_r1, 3, 256, 0);
     } else {
         add(w->head_w1, ws.wt_head1, d.c_out, 32, 0);
+        if (d.rot) add(w->head_r_w1, ws.wt_head_r1, 4, 32, 0);
     }
     add(w->head_w0, ws.wt_head0, d.hh, d.D, 0);
     add(w->mlp_w1, ws.wt_mlp1, d.D, d.hid, 0);
@@ -1257,15 +1269,20 @@ int da_train_forward(const da_weights *w, const da_graph *g, const float *x, con
 
 // One implementation behind the float-pose and the index entries.  x: float poses [n_real, c_in] (2D, 3D) or idx: position indices
 // [n_real] (discrete) -- exactly one of the two
+// (discrete rot).  rot_entry: the call came through da_train_forward_rot / da_train_backward_rot (out_rot / d_out_rot: the second head)
 static int train_backward_impl(const da_weights *w, const da_weights *grads, const da_graph *g, const float *x, const int32_t *idx,
                                const int64_t *t, const float *d_out, float *d_feats, void *workspace, size_t workspace_bytes,
-                               int mma_precision, int stage, void *stream);
+                               int mma_precision, int stage, void *stream, bool rot_entry = false, const float *d_out_rot = nullptr);
 static int train_forward_impl(const da_weights *w, const da_graph *g, const float *x, const int32_t *idx, const int64_t *t, const float *feats,
-                              float *out, void *workspace, size_t workspace_bytes, int mma_precision, void *stream) {
+                              float *out, void *workspace, size_t workspace_bytes, int mma_precision, void *stream, bool rot_entry = false,
+                              float *out_rot = nullptr) {
     Dims d;
     int rc;
     DA_REQUIRE(mma_precision == DA_TRAIN_MMA_FP32 || mma_precision == DA_TRAIN_MMA_BF16, "da_train_forward: unknown mma_precision %d", mma_precision);
     if ((rc = dims_of(w, g, d, mma_precision))) return rc;
+    DA_REQUIRE(rot_entry || !d.rot, "da_train_forward: a discrete rot denoiser has two heads (da_train_forward_rot / da_train_backward_rot)");
+    DA_REQUIRE(!rot_entry || d.rot, "da_train_forward_rot: not a discrete rot denoiser (variant %d; da_train_forward_idx / da_train_forward_ex)", w->variant);
+    DA_REQUIRE(!rot_entry || out_rot, "da_train_forward_rot: null argument");
     DA_REQUIRE(idx || !d.disc, "da_train_forward: a discrete denoiser takes position indices (da_train_forward_idx)");
     DA_REQUIRE(!idx || d.disc, "da_train_forward_idx: not a discrete denoiser (da_train_forward_ex takes poses)");
     DA_REQUIRE((x || idx) && t && feats && out && workspace, "da_train_forward: null argument");
@@ -1310,6 +1327,9 @@ static int train_forward_impl(const da_weights *w, const da_graph *g, const floa
         int r;
         if ((r = linear_fw(d, ws, nr, D, d.hh, zin, D, w->head_w0, w->head_b0, ws.f1pre, d.hh, st, ws.f1))) return r;
         if (d.v3d) return launch_head3d(P, nr, ws.f1, w->head_w1, w->head_b1, w->head_r_w1, w->head_r_b1, out, ws.pre6, st);
+        if (d.rot)         // Linear(32, K) over columns 0..31 and Linear(32, 4) over columns 32..63: the logits half of the rot sampling step's tail kernel
+            return launch_d3pm_rot_tail(P, nr, d.c_out, ws.f1, w->head_w1, w->head_b1, w->head_r_w1, w->head_r_b1, nullptr, nullptr, out, out_rot,
+                                        nullptr, st);
         if (d.disc) {      // Linear(32, K): the logits half of the sampling step's tail kernel (fp32 in both modes, row k of final_mlp.2 in registers)
             D3pmRows rows;
             rows.hh = ws.f1;
@@ -1411,6 +1431,20 @@ int da_train_backward_idx(const da_weights *w, const da_weights *grads, const da
     return train_backward_impl(w, grads, g, nullptr, idx, t, d_logits, d_feats, workspace, workspace_bytes, mma_precision, stage, stream);
 }
 
+int da_train_forward_rot(const da_weights *w, const da_graph *g, const int32_t *idx, const int64_t *t, const float *feats,
+                         float *logits, float *rot_logits, void *workspace, size_t workspace_bytes, int mma_precision, void *stream) {
+    DA_REQUIRE(idx && rot_logits, "da_train_forward_rot: null argument");
+    return train_forward_impl(w, g, nullptr, idx, t, feats, logits, workspace, workspace_bytes, mma_precision, stream, true, rot_logits);
+}
+
+int da_train_backward_rot(const da_weights *w, const da_weights *grads, const da_graph *g, const int32_t *idx, const int64_t *t,
+                          const float *d_logits, const float *d_rot_logits, float *d_feats, void *workspace, size_t workspace_bytes,
+                          int mma_precision, int stage, void *stream) {
+    DA_REQUIRE(idx && d_rot_logits, "da_train_backward_rot: null argument");
+    return train_backward_impl(w, grads, g, nullptr, idx, t, d_logits, d_feats, workspace, workspace_bytes, mma_precision, stage, stream, true,
+                               d_rot_logits);
+}
+
 int da_train_backward(const da_weights *w, const da_weights *grads, const da_graph *g, const float *x,
                       const int64_t *t, const float *d_out, float *d_feats, void *workspace, size_t workspace_bytes,
                       void *stream) {
@@ -1429,17 +1463,19 @@ int da_train_backward_ex(const da_weights *w, const da_weights *grads, const da_
 // virtual-node embedding, mlp, concat pieces.  EARLY then LATE on one stream == DA_TRAIN_BWD_ALL, launch for launch.
 static int train_backward_impl(const da_weights *w, const da_weights *grads, const da_graph *g, const float *x, const int32_t *idx,
                                const int64_t *t, const float *d_out, float *d_feats, void *workspace, size_t workspace_bytes,
-                               int mma_precision, int stage, void *stream) {
+                               int mma_precision, int stage, void *stream, bool rot_entry, const float *d_out_rot) {
     Dims d;
     DA_REQUIRE(stage == DA_TRAIN_BWD_ALL || stage == DA_TRAIN_BWD_EARLY || stage == DA_TRAIN_BWD_LATE, "da_train_backward_stage: unknown stage %d", stage);
     const bool do_early = stage != DA_TRAIN_BWD_LATE, do_late = stage != DA_TRAIN_BWD_EARLY;
     int rc;
     DA_REQUIRE(mma_precision == DA_TRAIN_MMA_FP32 || mma_precision == DA_TRAIN_MMA_BF16, "da_train_backward: unknown mma_precision %d", mma_precision);
     if ((rc = dims_of(w, g, d, mma_precision))) return rc;
+    DA_REQUIRE(rot_entry || !d.rot, "da_train_backward: a discrete rot denoiser has two heads (da_train_forward_rot / da_train_backward_rot)");
+    DA_REQUIRE(!rot_entry || d.rot, "da_train_backward_rot: not a discrete rot denoiser (variant %d; da_train_backward_idx / da_train_backward_stage)", w->variant);
     DA_REQUIRE(idx || !d.disc, "da_train_backward: a discrete denoiser takes position indices (da_train_backward_idx)");
     DA_REQUIRE(!idx || d.disc, "da_train_backward_idx: not a discrete denoiser (da_train_backward_stage takes poses)");
-    DA_REQUIRE(grads && (x || idx) && t && d_out && workspace, "da_train_backward: null argument");
-    DA_REQUIRE(!d.disc || (grads->variant == DA_VARIANT_DISCRETE && grads->c_out == w->c_out && grads->pos_w1), "da_train_backward_idx: grads must mirror the discrete weights");
+    DA_REQUIRE(grads && (x || idx) && t && (rot_entry ? d_out_rot : d_out) && workspace, "da_train_backward: null argument");
+    DA_REQUIRE(!d.disc || (grads->variant == w->variant && grads->c_out == w->c_out && grads->pos_w1), "da_train_backward_idx: grads must mirror the discrete weights");
     DA_REQUIRE(d.dense || (d.gcn && gcn_plan_kind(g) != 2) || (g->out_ptr && (g->out_dst || d.hybrid)), "da_train_backward: the graph needs the by-source CSR (out_ptr / "
                "out_dst; of the remainder edges for hybrid graphs, where out_dst may be empty)");
     if ((rc = check_fused(w, d, "da_train_backward(weights)"))) return rc;
@@ -1467,6 +1503,19 @@ static int train_backward_impl(const da_weights *w, const da_weights *grads, con
         if ((rc = linear_bwd(nr, 3, 256, ws.dpre6 + 3, 6, ws.f1, 512, ws.wt_head1, G(grads->head_w1), G(grads->head_b1),
                              ws.df1, 512, nullptr, ws, st, d.bfc, false, nullptr, nullptr, sd))) return rc;
         if ((rc = gelu_bwd((size_t)nr * 512, ws.f1pre, ws.df1, ws.df1, st))) return rc;
+    } else if (d.rot) {
+        // two heads (efficient_gat_discrete_rotation.py:111-114): final_mlp.2 over columns 0..31 and final_mlp_rot.2 over columns 32..63 of the
+        // 64-wide hidden layer (leading dimension 64, the 3D heads' pattern), then one GELU backward over both halves.  d_out == NULL
+        // (only_rotation): no position-head products; its half of the hidden gradient is zero
+        if (d_out) {
+            if ((rc = linear_bwd(nr, d.c_out, 32, d_out, d.c_out, ws.f1, 64, ws.wt_head1, G(grads->head_w1), G(grads->head_b1),
+                                 ws.df1, 64, nullptr, ws, st, d.bfc, false, nullptr, nullptr, sd))) return rc;
+        } else {
+            DA_CHECK_HIP(hipMemset2DAsync(ws.df1, 64 * sizeof(float), 0, 32 * sizeof(float), (size_t)nr, st));
+        }
+        if ((rc = linear_bwd(nr, 4, 32, d_out_rot, 4, ws.f1 + 32, 64, ws.wt_head_r1, G(grads->head_r_w1), G(grads->head_r_b1),
+                             ws.df1 + 32, 64, nullptr, ws, st, d.bfc, false, nullptr, nullptr, sd))) return rc;
+        if ((rc = gelu_bwd((size_t)nr * 64, ws.f1pre, ws.df1, ws.df1, st))) return rc;
     } else
     if ((rc = linear_bwd(nr, d.c_out, 32, d_out, d.c_out, ws.f1, 32, ws.wt_head1, G(grads->head_w1), G(grads->head_b1),
                          ws.df1, 32, nullptr, ws, st, d.bfc, false, ws.f1pre, nullptr, sd))) return rc;

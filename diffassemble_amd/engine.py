@@ -657,9 +657,11 @@ class DenoiserEngine:
 def d3pm_noise(seed, iteration, n, K, domain="sampling"):
     """The uniforms the discrete reverse step (``domain="sampling"``) or the training-side noising of ``d3pm_q_sample``
     (``domain="training"``) draws for itself from ``seed`` (int64 [2] device tensor {seed, offset}): [n, K] fp32 in (0, 1]
-    (da_d3pm_noise_ex).  The two domains never share a stream."""
+    (da_d3pm_noise_ex).  The two domains never share a stream; ``"sampling_rot"`` / ``"training_rot"`` are the rotation halves'
+    streams of the position + rotation model ([n, 4])."""
     u = torch.empty((n, K), dtype=torch.float32, device=seed.device)
-    dom = {"sampling": _lib.D3PM_DRAW_SAMPLING, "training": _lib.D3PM_DRAW_TRAINING, "sampling_rot": _lib.D3PM_DRAW_SAMPLING_ROT}[domain]
+    dom = {"sampling": _lib.D3PM_DRAW_SAMPLING, "training": _lib.D3PM_DRAW_TRAINING, "sampling_rot": _lib.D3PM_DRAW_SAMPLING_ROT,
+           "training_rot": _lib.D3PM_DRAW_TRAINING_ROT}[domain]
     with torch.cuda.device(seed.device):
         _lib.check(_lib.lib().da_d3pm_noise_ex(_lib.ptr(seed), int(iteration), int(n), int(K), dom, _lib.ptr(u), _lib.stream_ptr(seed.device)))
     return u
@@ -708,6 +710,71 @@ def d3pm_loss(sched: Schedule, logits, x_start, x_t, t, kind="vb", lambda_loss=0
         _lib.check(_lib.lib().da_d3pm_loss(C.byref(sched.c), n, K, _lib.D3PM_LOSS[kind], float(lambda_loss), _lib.ptr(z), _lib.ptr(x0),
                                            _lib.ptr(xt), _lib.ptr(tt), _lib.ptr(loss), _lib.ptr(d_logits), _lib.ptr(rows), _lib.stream_ptr(dev)))
     return loss, d_logits, rows
+
+
+def d3pm_q_sample_rot(sched: Schedule, x_start, rot_start, t, K, noise_x=None, noise_rot=None, seed=None, iteration=0, want_x=True):
+    """Both forward noisings of the position + rotation model in one launch (da_d3pm_q_sample_rot): x_start / rot_start [N]
+    indices, t [N] int64 on a ROCm device -> (x_t [N] int64 or None, rot_t [N] int64).  ``noise_x`` [N, K] / ``noise_rot`` [N, 4]
+    uniforms, or ``seed`` (int64 [2] device tensor) for the kernel's own draws (training / training_rot domains).
+    ``want_x=False`` skips the position half (only_rotation): ``x_start`` may then be None."""
+    dev = rot_start.device
+    if dev.type != "cuda":
+        raise _lib.DaError("d3pm_q_sample_rot needs ROCm tensors (no CPU path in diffassemble_amd)")
+    i32 = lambda x: x.detach().to(device=dev, dtype=torch.int32).contiguous()      # noqa: E731
+    r0 = i32(rot_start)
+    n = r0.shape[0]
+    x0 = i32(x_start) if want_x else None
+    tt = t.detach().to(device=dev, dtype=torch.int64).contiguous()
+    nx = None if noise_x is None or not want_x else _f32(noise_x, dev)
+    nr = None if noise_rot is None else _f32(noise_rot, dev)
+    if tt.shape != (n,) or (x0 is not None and x0.shape != (n,)) or (nx is not None and nx.shape != (n, int(K))) or \
+            (nr is not None and nr.shape != (n, 4)):
+        raise _lib.DaError(f"d3pm_q_sample_rot: shapes rot_start {tuple(r0.shape)}, x_start {None if x0 is None else tuple(x0.shape)}, "
+                           f"t {tuple(tt.shape)}, noise_x {None if nx is None else tuple(nx.shape)}, noise_rot {None if nr is None else tuple(nr.shape)}, K {K}")
+    xn = torch.empty(n, dtype=torch.int32, device=dev) if want_x else None
+    rn = torch.empty(n, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().da_d3pm_q_sample_rot(C.byref(sched.c), n, int(K), _lib.ptr(x0), _lib.ptr(r0), _lib.ptr(tt), _lib.ptr(nx),
+                                                   _lib.ptr(nr), _lib.ptr(seed), int(iteration), _lib.ptr(xn), _lib.ptr(rn),
+                                                   _lib.stream_ptr(dev)))
+    return (xn.long() if want_x else None), rn.long()
+
+
+def d3pm_rot_loss(sched: Schedule, logits, rot_logits, x_start, x_t, rot_start, rot_t, t, kind="vb", lambda_loss=0.01, d_logits=None):
+    """Both heads' loss of the position + rotation p_losses and its gradients in one call (da_d3pm_rot_loss): logits [N, K] (or
+    None: only_rotation, the position half is skipped) and rot_logits [N, 4] fp32, the four index vectors and t [N] on a ROCm
+    device.  Returns (loss [6] = {x_loss, rot_loss, x_vb, x_ce, rot_vb, rot_ce}, d_logits [N, K] or None, d_rot_logits [N, 4],
+    row_terms [N, 4]); the gradients are for unit upstream gradients of x_loss / rot_loss.  ``d_logits``: a caller's buffer."""
+    dev = rot_logits.device
+    if dev.type != "cuda":
+        raise _lib.DaError("d3pm_rot_loss needs ROCm tensors (no CPU path in diffassemble_amd)")
+    if kind not in _lib.D3PM_LOSS:
+        raise _lib.DaError(f"d3pm_rot_loss: kind {kind!r} is not one of {sorted(_lib.D3PM_LOSS)}")
+    i32 = lambda x: x.detach().to(device=dev, dtype=torch.int32).contiguous()      # noqa: E731
+    zr = _f32(rot_logits, dev)
+    n = zr.shape[0]
+    r0, rt = i32(rot_start), i32(rot_t)
+    tt = t.detach().to(device=dev, dtype=torch.int64).contiguous()
+    if zr.shape != (n, 4) or not (r0.shape == rt.shape == tt.shape == (n,)):
+        raise _lib.DaError(f"d3pm_rot_loss: rot_logits {tuple(zr.shape)} against rot_start {tuple(r0.shape)}, rot_t {tuple(rt.shape)}, t {tuple(tt.shape)}")
+    z = x0 = xt = None
+    K = 2
+    if logits is not None:
+        z, x0, xt = _f32(logits, dev), i32(x_start), i32(x_t)
+        K = z.shape[1]
+        if z.shape[0] != n or not (x0.shape == xt.shape == (n,)):
+            raise _lib.DaError(f"d3pm_rot_loss: logits {tuple(z.shape)} against x_start {tuple(x0.shape)}, x_t {tuple(xt.shape)}, n {n}")
+        if d_logits is None:
+            d_logits = torch.empty_like(z)
+    loss = torch.empty(6, dtype=torch.float32, device=dev)
+    d_rot = torch.empty_like(zr)
+    rows = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().da_d3pm_rot_loss(C.byref(sched.c), n, K, _lib.D3PM_LOSS[kind], float(lambda_loss), _lib.ptr(z), _lib.ptr(zr),
+                                               _lib.ptr(x0), _lib.ptr(xt), _lib.ptr(r0), _lib.ptr(rt), _lib.ptr(tt), _lib.ptr(loss),
+                                               _lib.ptr(d_logits), _lib.ptr(d_rot), _lib.ptr(rows),
+                                               _lib.stream_ptr(dev)))
+    return loss, (d_logits if z is not None else None), d_rot, rows
 
 
 def d3pm_step(sched: Schedule, x_t, logits, t, ratio, noise=None, seed=None, iteration=0, return_post=False):

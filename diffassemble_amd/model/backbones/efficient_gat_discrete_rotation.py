@@ -1,7 +1,9 @@
 """Counterpart of puzzle_diff/model/backbones/efficient_gat_discrete_rotation.py (``Eff_GAT_Discrete_ROT``): the denoiser of the
 discrete position + rotation diffusion -- ``Eff_GAT_Discrete`` with a second, 4-wide head ``final_mlp_rot``.  Same constructor
 arguments, attribute and state-dict names; ``forward_with_feats`` runs as ONE call into the HIP library and returns
-``(logits [N, K], rot_logits [N, 4])``.  Inference only: the two-head backward is not built.
+``(logits [N, K], rot_logits [N, 4])``.  Under grad (``train()`` mode with trainable parameters) the forward and its backward run
+through ``DenoiserTrainFn2`` over da_train_forward_rot / da_train_backward_rot, on ROCm tensors only: the first layer of both heads is
+one 64-wide product each way, and a head whose logits take no part in the loss costs no second-layer products.
 
 Differences from the reference, on purpose:
 * the reference's ``forward_with_feats`` raises as shipped (:106-110 adds the ``(x, attentions)`` pair ``Transformer_GNN`` returns to
@@ -16,10 +18,12 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
+from ...train import DenoiserTrainFn2
 from ._denoiser_base import _Held
 from .efficient_gat_discrete import Eff_GAT_Discrete
 
 _NOT_BUILT = "discrete-rotation training is not built yet"
+_OFF_DEVICE = _NOT_BUILT + " off the device: it runs on ROCm tensors only (diffassemble_amd has no CPU path)"
 
 
 class Eff_GAT_Discrete_ROT(Eff_GAT_Discrete):
@@ -41,9 +45,15 @@ class Eff_GAT_Discrete_ROT(Eff_GAT_Discrete):
     def forward_with_feats(self, xy_pos: Tensor, rot: Tensor, time: Tensor, patch_rgb: Tensor, edge_index: Tensor, patch_feats: Tensor,
                            batch, rot_acc=None):
         """efficient_gat_discrete_rotation.py:87-115 -> (logits [N, K], rot_logits [N, 4]) fp32.  ``rot`` is not read (the reference's
-        network does not read it either); ``rot_acc`` needs ``patch_feats`` [4, N, 1088]."""
+        network does not read it either); ``rot_acc`` needs ``patch_feats`` [4, N, 1088].  Under grad: the training route, one feature
+        image ``patch_feats`` [N, 1088] and no ``rot_acc`` (the reference's p_losses encodes the unrotated crops once); both outputs
+        require grad."""
         if self._wants_grad():
-            raise NotImplementedError(_NOT_BUILT)
+            if not all(torch.is_tensor(v) and v.is_cuda for v in (xy_pos, time, edge_index, patch_feats)):
+                raise NotImplementedError(_OFF_DEVICE)
+            if rot_acc is not None or patch_feats.dim() != 2:
+                raise ValueError("training reads one feature image: patch_feats [N, 1088] and rot_acc=None")
+            return self._run_train2(xy_pos, time, edge_index, patch_feats, batch)
         if rot_acc is not None and patch_feats.dim() != 3:
             raise ValueError("rot_acc needs the four feature images: patch_feats [4, N, 1088]")
         with torch.no_grad():
@@ -51,6 +61,16 @@ class Eff_GAT_Discrete_ROT(Eff_GAT_Discrete):
             plan = self._plan_for(eng, edge_index, batch)
             self._stage_features(eng, plan, patch_feats)
             return eng.forward_rot(plan, xy_pos, time, None, rot_acc=rot_acc)
+
+    def _run_train2(self, xy_pos, time, edge_index, feats, batch):
+        """``DenoiserBase._run_train`` with two outputs."""
+        te = self.train_engine(xy_pos.device)
+        key = getattr(self, "_tplan_key", None)
+        if key is None or not key.matches((edge_index, batch), (id(te),)):
+            from ...graph_plan import build_plan
+            self._tplan = build_plan(edge_index.to(te.device), batch.to(te.device), te.virt_nodes).with_source_csr()
+            self._tplan_key = _Held((edge_index, batch), (id(te),))
+        return DenoiserTrainFn2.apply(te, self._tplan, xy_pos, time, feats, te.anchor)
 
     def _stage_features(self, eng, plan, feats):
         key = getattr(self, "_feat_key", None)

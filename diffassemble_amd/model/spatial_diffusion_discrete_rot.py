@@ -1,9 +1,14 @@
 """Counterpart of puzzle_diff/model/spatial_diffusion_discrete_rot.py: ``GNN_Diffusion`` of the discrete position + rotation
 diffusion (two D3PM processes with the uniform transition, K positions and ``rot_K = 4`` quarter turns, over
-``backbones.Eff_GAT_Discrete_ROT``), with the reference's constructor, attributes and Lightning hooks.  Inference only: forward,
-reverse step, the captured sampling loop, validation / test / predict steps, on a ROCm device.
+``backbones.Eff_GAT_Discrete_ROT``), with the reference's constructor, attributes and Lightning hooks: inference (forward, reverse
+step, the captured sampling loop, validation / test / predict steps) and training (``q_sample`` / ``q_sample_rot``, ``p_losses``,
+``vb_terms_bpd``, ``training_step``), both on a ROCm device only -- off the device the training methods raise
+``NotImplementedError``, as the project has no CPU path.
 
-* ``forward_with_feats`` -> one ``da_denoiser_forward_rot`` call -> (logits [N, K], rot_logits [N, 4])
+* ``forward_with_feats`` -> one ``da_denoiser_forward_rot`` call -> (logits [N, K], rot_logits [N, 4]); under grad
+                            ``da_train_forward_rot`` / ``da_train_backward_rot``
+* ``p_losses``           -> ``da_d3pm_q_sample_rot`` (both noisings, one launch), the two-head training forward, and
+                            ``da_d3pm_rot_loss``: both losses and both logit gradients in one call
 * ``p_sample_ddpm``      -> forward + ``da_d3pm_rot_step`` -> the reference's triple (index, rot_0, rot_prev_t)
 * ``p_sample_loop``      -> ``da_sample_loop_rot``: every iteration enqueued by one C call, replayed as one hipGraph launch
 
@@ -16,7 +21,15 @@ Differences from the reference, on purpose (besides those of ``spatial_diffusion
 * the reference backbone's ``forward_with_feats`` raises as shipped; this module computes what it computes once the
   ``(x, attentions)`` pair of ``Transformer_GNN`` is unpacked (DESIGN.md 1);
 * no classifier-free branch at inference (the reference has none either), no image dumps;
-* ``p_losses`` / ``training_step`` raise ``NotImplementedError``: the two-head training path is not built.
+* training: the network reads neither ``rot_noisy`` nor ``rot_start`` (the reference's ``rotate_images`` line is commented out, :184),
+  so ``p_losses`` encodes the crops once and trains on ONE feature image [N, 1088], not on the four of the sampling loop;
+* ``training_step`` takes ``rot_start = batch.rot_index % self.rot_K``; the reference writes ``% self.K`` (:87), which is the same value
+  for every K >= 4 (rot_index lies in {0..3}) and an out-of-range class for a 2- or 3-piece puzzle;
+* ``"cross_entropy"`` smooths neither head and ``"hybrid"`` smooths the position head's cross entropy only (:208-273), unlike the
+  position module, which smooths in both kinds;
+* under ``only_rotation`` the position draw of the reference ([N, K] uniforms that nothing reads) is not made, the position head's
+  second-layer products are skipped, and ``final_mlp.*`` receive a ZERO gradient where the reference leaves ``None``: an Adafactor step
+  leaves those parameters bit-equal either way.
 """
 import torch
 
@@ -25,6 +38,35 @@ from . import spatial_diffusion_discrete as sdd
 
 _Q_TABLES = sdd._Q_TABLES + ("overline_Q_rot",)
 _NOT_BUILT = "discrete-rotation training is not built yet"
+_OFF_DEVICE = _NOT_BUILT + " off the device: it runs on ROCm tensors only (diffassemble_amd has no CPU path)"
+
+
+def _require_device(*tensors):
+    """The training methods' guard: every argument must be a tensor on a ROCm device."""
+    if not tensors or not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
+        raise NotImplementedError(_OFF_DEVICE)
+
+
+class _D3pmRotLoss(torch.autograd.Function):
+    """Both heads' losses with their gradients with respect to both logits computed in the SAME call (da_d3pm_rot_loss), like
+    ``spatial_diffusion_discrete._D3pmLoss``: backward scales ``d_logits`` by the upstream gradient of ``x_loss`` and ``d_rot_logits``
+    by that of ``rot_loss``.  ``logits`` None (only_rotation): the position half is skipped.  Returns (x_loss, rot_loss, parts [6])."""
+
+    @staticmethod
+    def forward(ctx, logits, rot_logits, sched, x_start, x_t, rot_start, rot_t, t, kind, lambda_loss):
+        from ..engine import d3pm_rot_loss
+        loss, d_logits, d_rot, _ = d3pm_rot_loss(sched, logits, rot_logits, x_start, x_t, rot_start, rot_t, t, kind, lambda_loss)
+        ctx.has_x = d_logits is not None
+        ctx.save_for_backward(*((d_logits, d_rot) if ctx.has_x else (d_rot,)))
+        parts = loss.clone()
+        ctx.mark_non_differentiable(parts)
+        return loss[0].clone(), loss[1].clone(), parts
+
+    @staticmethod
+    def backward(ctx, g_x, g_rot, _g_parts):
+        d_rot = ctx.saved_tensors[-1]
+        d_logits = ctx.saved_tensors[0] * g_x if ctx.has_x else None
+        return (d_logits, d_rot * g_rot) + (None,) * 8
 
 
 class GNN_Diffusion(sdd.GNN_Diffusion):
@@ -43,12 +85,77 @@ class GNN_Diffusion(sdd.GNN_Diffusion):
         state_dict.pop(prefix + "overline_Q_rot", None)           # (the parent drops its own three tables)
         return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
-    # ------------------------------------------------------------------ training side: not built
+    # ------------------------------------------------------------------ training side (ROCm device only)
     def training_step(self, batch=None, batch_idx=0):
-        raise NotImplementedError(_NOT_BUILT)
+        """spatial_diffusion_discrete_rot.py:75-145 without the ``batch_idx == 0`` sampling-and-image dump: logs the dict of
+        ``p_losses`` and ``"loss"`` = their sum, returns the sum."""
+        if batch is None or not hasattr(batch, "batch"):
+            raise NotImplementedError(_OFF_DEVICE)
+        _require_device(batch.batch, batch.indexes, batch.rot_index)
+        batch_size = batch.batch.max().item() + 1
+        t = torch.randint(0, self.steps, (batch_size,), device=self.device).long()
+        new_t = torch.gather(t, 0, batch.batch)
+        losses = self.p_losses(batch.indexes % self.K, new_t, rot_start=batch.rot_index % self.rot_K, loss_type=self.loss_type,
+                               cond=batch.patches, edge_index=batch.edge_index, batch=batch.batch,
+                               patch_feats=getattr(batch, "patch_feats", None))
+        self.log_dict(losses)
+        loss_tot = sum(l for l in losses.values())
+        self.log("loss", loss_tot)
+        return loss_tot
 
-    def p_losses(self, *args, **kwargs):
-        raise NotImplementedError(_NOT_BUILT)
+    def q_sample_rot(self, rot_start=None, t=None, noise=None):
+        """The rotation process' q_sample (``q_sample(one_hot(rot_start, 4), t, overline_Q_rot)``, :181-183) in closed form:
+        ``rot_start`` [N] in {0..3}, ``t`` [N] -> rot_t [N] int64.  ``noise`` (extension): the [N, 4] uniforms; default: drawn
+        inside the kernel (training_rot domain)."""
+        _require_device(rot_start, t)
+        from ..engine import d3pm_q_sample_rot
+        seed = None if noise is not None else self._train_seed_tensor(rot_start.device)
+        return d3pm_q_sample_rot(self._schedule(), None, rot_start, t, self.K, noise_rot=noise, seed=seed, want_x=False)[1]
+
+    def vb_terms_bpd(self, pred_x_start_logits=None, model_logits=None, x_start=None, x_t=None, t=None, K=None, overline_Q=None):
+        """spatial_diffusion_discrete_rot.py's two uses of vb_terms_bpd: ``K=None`` / ``K=self.K`` evaluates the position process,
+        ``K=self.rot_K`` the rotation process (da_d3pm_loss at K = 4; ``overline_Q`` is accepted there for the reference's signature
+        and not read: the closed form serves both)."""
+        if K is not None and K == self.rot_K and K != self.K:
+            _require_device(pred_x_start_logits, x_start, x_t, t)
+            if pred_x_start_logits.shape[-1] != self.rot_K:
+                raise ValueError(f"vb_terms_bpd(K={K}): logits of shape {tuple(pred_x_start_logits.shape)}")
+            return sdd._D3pmLoss.apply(pred_x_start_logits, self._schedule(), x_start, x_t, t, "vb", float(self.lambda_loss))[0]
+        return super().vb_terms_bpd(pred_x_start_logits, model_logits, x_start, x_t, t, K=K, overline_Q=overline_Q)
+
+    def p_losses(self, x_start=None, t=None, rot_start=None, noise=None, loss_type="l1", cond=None, edge_index=None, batch=None,
+                 cfg_rand=None, patch_feats=None, noise_rot=None):
+        """spatial_diffusion_discrete_rot.py:161-279 -> ``{"x_loss", "rot_loss"}`` filtered by ``losses_keys``, differentiable scalars.
+        ``x_start`` [N] position indices, ``rot_start`` [N] in {0..3}, ``t`` [N].  Extensions for parity runs: ``noise`` [N, K] /
+        ``noise_rot`` [N, 4] uniforms of the two noisings (default in-kernel draws), ``cfg_rand`` [G] uniforms of the classifier-free
+        mask, ``patch_feats`` [N, 1088] bypasses the piece encoder.  ``self.last_loss_parts``: the [6] device tensor {x_loss,
+        rot_loss, x_vb, x_ce, rot_vb, rot_ce} of the last call; ``self.last_noisy``: its (x_noisy, rot_noisy)."""
+        _require_device(x_start, t, rot_start)
+        if loss_type not in sdd._LOSS_TYPES:
+            raise Exception("Loss not implemented %s", loss_type)
+        _require_device(edge_index, batch)
+        from ..engine import d3pm_q_sample_rot
+        only_rot = bool(self.only_rotation)
+        need_seed = noise_rot is None or (noise is None and not only_rot)
+        seed = self._train_seed_tensor(x_start.device) if need_seed else None
+        x_noisy, rot_noisy = d3pm_q_sample_rot(self._schedule(), x_start, rot_start, t, self.K, noise_x=noise, noise_rot=noise_rot,
+                                               seed=seed, want_x=not only_rot)
+        if only_rot:
+            x_noisy = x_start
+        self.last_noisy = (x_noisy, rot_noisy)
+        if patch_feats is None:
+            patch_feats = self.visual_features(cond)
+        if cfg_rand is not None or self.classifier_free_prob > 0.0:
+            if cfg_rand is None:
+                cfg_rand = torch.rand(int(batch.max()) + 1, device=batch.device)
+            keep = cfg_rand.to(batch.device)[batch] > self.classifier_free_prob
+            patch_feats = keep[:, None] * patch_feats
+        x_pred, rot_pred = self.forward_with_feats(x_noisy, t, cond, edge_index, patch_feats, rot_noisy, batch)
+        x_loss, rot_loss, parts = _D3pmRotLoss.apply(None if only_rot else x_pred, rot_pred, self._schedule(), x_start, x_noisy,
+                                                     rot_start, rot_noisy, t, loss_type, float(self.lambda_loss))
+        self.last_loss_parts = parts
+        losses = {"x_loss": x_loss, "rot_loss": rot_loss}
+        return {k: v for k, v in losses.items() if k in self.losses_keys}
 
     # ------------------------------------------------------------------ reverse process
     def forward_with_feats(self, xy_pos, time, patch_rgb, edge_index, patch_feats, rot, batch, rot_acc=None):

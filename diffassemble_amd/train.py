@@ -33,9 +33,9 @@ from .graph_plan import GraphPlan
 
 def _param_order(module):
     """(names in flat-buffer order, number of conv layers); names relative to the Eff_GAT / Eff_GAT_3d / Eff_GAT_Discrete module.
-    The discrete variant has the embedding table ``pos_mlp.weight`` [K, 32] where the pose MLP's four tensors were, and a K-row
-    ``final_mlp.2``."""
-    pos = ["pos_mlp.weight"] if getattr(module, "variant", "2d") == "discrete" else \
+    The discrete variants have the embedding table ``pos_mlp.weight`` [K, 32] where the pose MLP's four tensors were, and a K-row
+    ``final_mlp.2``; ``discrete_rot`` adds the rotation head ``final_mlp_rot``."""
+    pos = ["pos_mlp.weight"] if getattr(module, "variant", "2d") in ("discrete", "discrete_rot") else \
         ["pos_mlp.0.weight", "pos_mlp.0.bias", "pos_mlp.2.weight", "pos_mlp.2.bias"]
     names = ["time_emb.weight"] + pos + ["mlp.0.weight", "mlp.0.bias", "mlp.2.weight", "mlp.2.bias"]
     n_layers = len(module.gnn_backbone.module_list)
@@ -55,13 +55,19 @@ def _param_order(module):
         # is ONE gap-free slot -- the trick of the lin_query | key | value | skip groups
         names += ["mlp_t.0.weight", "mlp_r.0.weight", "mlp_t.0.bias", "mlp_r.0.bias",
                   "mlp_t.2.weight", "mlp_t.2.bias", "mlp_r.2.weight", "mlp_r.2.bias"]
+    elif getattr(module, "variant", "2d") == "discrete_rot":
+        # Eff_GAT_Discrete_ROT's two heads: final_mlp.0 | final_mlp_rot.0 adjacent (weights, then biases), so the 64-row first layer of
+        # both heads is ONE gap-free slot, as above
+        names += ["final_mlp.0.weight", "final_mlp_rot.0.weight", "final_mlp.0.bias", "final_mlp_rot.0.bias",
+                  "final_mlp.2.weight", "final_mlp.2.bias", "final_mlp_rot.2.weight", "final_mlp_rot.2.bias"]
     else:
         names += ["final_mlp.0.weight", "final_mlp.0.bias", "final_mlp.2.weight", "final_mlp.2.bias"]
     return names, n_layers
 
 
 class TrainEngine:
-    """Owns the flat buffers + training workspace of one ``Eff_GAT`` / ``Eff_GAT_3d`` / ``Eff_GAT_Discrete`` module on one GPU."""
+    """Owns the flat buffers + training workspace of one ``Eff_GAT`` / ``Eff_GAT_3d`` / ``Eff_GAT_Discrete`` / ``Eff_GAT_Discrete_ROT``
+    module on one GPU."""
 
     def __init__(self, module, device=None):
         self.lib = _lib.lib()
@@ -78,7 +84,7 @@ class TrainEngine:
         offs, off = [], 0
         for n, p in zip(names, self.params):
             fused_tail = any(n.endswith(f"lin_{k}.{w}") for k in ("key", "value", "skip") for w in ("weight", "bias")) \
-                or n in ("mlp_r.0.weight", "mlp_r.0.bias")
+                or n in ("mlp_r.0.weight", "mlp_r.0.bias", "final_mlp_rot.0.weight", "final_mlp_rot.0.bias")
             if not fused_tail:
                 off = (off + 63) // 64 * 64            # 256-byte aligned slots; fused groups stay gap-free
             offs.append(off)
@@ -106,7 +112,8 @@ class TrainEngine:
         by = dict(zip(names, self.views))
         self.D = by["mlp.0.weight"].shape[1]
         self.F = self.D - 64
-        self.c_in = 1 if self.variant == "discrete" else by["pos_mlp.0.weight"].shape[1]      # discrete: one position index per piece
+        self.disc = self.variant in ("discrete", "discrete_rot")
+        self.c_in = 1 if self.disc else by["pos_mlp.0.weight"].shape[1]      # discrete: one position index per piece
         self.c_out = 7 if self.variant == "3d" else by["final_mlp.2.weight"].shape[0]        # 3D: unit quaternion wxyz | translation
         self.steps = by["time_emb.weight"].shape[0]
         self.hidden = by["mlp.0.weight"].shape[0]
@@ -163,13 +170,13 @@ class TrainEngine:
 
     def _weights_struct(self, by):
         w = _lib.DaWeights()
-        w.variant = {"3d": _lib.VARIANT_3D, "discrete": _lib.VARIANT_DISCRETE}.get(self.variant, _lib.VARIANT_2D)
+        w.variant = {"3d": _lib.VARIANT_3D, "discrete": _lib.VARIANT_DISCRETE, "discrete_rot": _lib.VARIANT_DISCRETE_ROT}.get(self.variant, _lib.VARIANT_2D)
         w.arch = {"exophormer": _lib.ARCH_EXOPHORMER, "gcn": _lib.ARCH_GCN}.get(self.arch, _lib.ARCH_TRANSFORMER)
         w.steps, w.c_in, w.c_out, w.feat_dim, w.hidden = self.steps, self.c_in, self.c_out, self.F, self.hidden
         w.heads, w.n_layers, w.virt_nodes = 8, self.n_layers, self.virt_nodes
         P = lambda n: by[n].data_ptr()  # noqa: E731
         w.time_emb = P("time_emb.weight")
-        if self.variant == "discrete":
+        if self.disc:
             w.pos_w1 = P("pos_mlp.weight")                 # [K, 32]; pos_w0 / pos_b0 / pos_b1 stay NULL (da_weights, DA_VARIANT_DISCRETE)
         else:
             w.pos_w0, w.pos_b0, w.pos_w1, w.pos_b1 = (P("pos_mlp.0.weight"), P("pos_mlp.0.bias"), P("pos_mlp.2.weight"),
@@ -194,6 +201,9 @@ class TrainEngine:
             return w
         w.head_w0, w.head_b0 = P("final_mlp.0.weight"), P("final_mlp.0.bias")
         w.head_w1, w.head_b1 = P("final_mlp.2.weight"), P("final_mlp.2.bias")
+        if self.variant == "discrete_rot":
+            w.head_r_w0, w.head_r_b0 = P("final_mlp_rot.0.weight"), P("final_mlp_rot.0.bias")
+            w.head_r_w1, w.head_r_b1 = P("final_mlp_rot.2.weight"), P("final_mlp_rot.2.bias")
         return w
 
     # ------------------------------------------------------------------ plumbing
@@ -247,8 +257,9 @@ class TrainEngine:
 
     def forward(self, plan: GraphPlan, x, t, feats):
         """da_train_forward: out [n_real, c_out] fp32; activations stay in the workspace for backward.  Discrete variant: ``x``
-        holds the position indices [n_real] and ``out`` the logits [n_real, K] (da_train_forward_idx)."""
-        disc = self.variant == "discrete"
+        holds the position indices [n_real] and ``out`` the logits [n_real, K] (da_train_forward_idx); ``discrete_rot``: returns the
+        pair (logits [n_real, K], rot_logits [n_real, 4]) (da_train_forward_rot)."""
+        disc = self.disc
         x = x.detach().to(self.device, torch.int32 if disc else torch.float32).contiguous()
         t = t.detach().to(self.device, torch.int64).contiguous()
         feats = feats.detach().to(self.device, torch.float32).contiguous()
@@ -258,6 +269,12 @@ class TrainEngine:
         g = self._cg(plan)
         fwd = self.lib.da_train_forward_idx if disc else self.lib.da_train_forward_ex
         with torch.cuda.device(self.device):
+            if self.variant == "discrete_rot":
+                out_rot = torch.empty((plan.n_real, 4), dtype=torch.float32, device=self.device)
+                _lib.check(self.lib.da_train_forward_rot(C.byref(self.w), C.byref(g), _lib.ptr(x), _lib.ptr(t), _lib.ptr(feats), _lib.ptr(out),
+                                                         _lib.ptr(out_rot), _lib.ptr(ws), ws.numel(), self._mma(), _lib.stream_ptr(self.device)))
+                self._fwd_mma = self._mma()
+                return out, out_rot
             _lib.check(fwd(C.byref(self.w), C.byref(g), _lib.ptr(x), _lib.ptr(t), _lib.ptr(feats),
                            _lib.ptr(out), _lib.ptr(ws), ws.numel(), self._mma(), _lib.stream_ptr(self.device)))
         self._fwd_mma = self._mma()
@@ -268,9 +285,11 @@ class TrainEngine:
             raise _lib.DaError(f"TrainEngine.precision must be 'fp32' or 'bf16', not {self.precision!r}")
         return _lib.TRAIN_MMA_BF16 if self.precision == "bf16" else _lib.TRAIN_MMA_FP32
 
-    def backward(self, plan: GraphPlan, x, t, d_out, want_dfeats=False):
+    def backward(self, plan: GraphPlan, x, t, d_out, want_dfeats=False, d_out_rot=None):
         """da_train_backward: adds every parameter gradient into ``flat_grad`` (and attaches the views
-        as ``.grad``); returns d_feats [n_real, F] or None.
+        as ``.grad``); returns d_feats [n_real, F] or None.  ``discrete_rot``: ``d_out`` / ``d_out_rot`` are the gradients of the two
+        heads' logits (da_train_backward_rot); either may be None -- a missing ``d_out`` skips the position head's products
+        (only_rotation: ``final_mlp.*`` get a zero gradient), a missing ``d_out_rot`` counts as zeros.
 
         COLLECTIVE under the bucketed exchange: with an initialised multi-rank process group and ``overlap_exchange`` (the
         default), this call issues the early bucket's all-reduce on the side stream -- every rank must then run the SAME number
@@ -285,10 +304,18 @@ class TrainEngine:
         if not attached:
             self.flat_grad.zero_()
         self.grads_synced = False
-        disc = self.variant == "discrete"
+        disc, rot = self.disc, self.variant == "discrete_rot"
         x = x.detach().to(self.device, torch.int32 if disc else torch.float32).contiguous()
         t = t.detach().to(self.device, torch.int64).contiguous()
-        d_out = d_out.detach().to(self.device, torch.float32).contiguous()
+        if rot:
+            if d_out is None and d_out_rot is None:
+                raise _lib.DaError("TrainEngine.backward (discrete_rot): both logit gradients are None")
+            if d_out_rot is None:
+                d_out_rot = torch.zeros((plan.n_real, 4), dtype=torch.float32, device=self.device)
+            d_out_rot = d_out_rot.detach().to(self.device, torch.float32).contiguous()
+            assert d_out_rot.shape == (plan.n_real, 4) and (d_out is None or d_out.shape == (plan.n_real, self.c_out))
+        if d_out is not None:
+            d_out = d_out.detach().to(self.device, torch.float32).contiguous()
         bwd = self.lib.da_train_backward_idx if disc else self.lib.da_train_backward_stage
         d_feats = torch.empty((plan.n_real, self.F), dtype=torch.float32, device=self.device) if want_dfeats else None
         mma = getattr(self, "_fwd_mma", self._mma())       # the mode of the forward it follows
@@ -298,9 +325,14 @@ class TrainEngine:
         staged = overlap or getattr(self, "force_staged", False)       # (force_staged: tests -- the two halves without a process group)
         with torch.cuda.device(self.device):
             for stage in ((_lib.TRAIN_BWD_EARLY, _lib.TRAIN_BWD_LATE) if staged else (_lib.TRAIN_BWD_ALL,)):
-                _lib.check(bwd(C.byref(self.w), C.byref(self.gw), C.byref(g), _lib.ptr(x), _lib.ptr(t),
-                               _lib.ptr(d_out), _lib.ptr(d_feats), _lib.ptr(ws), ws.numel(), mma, stage,
-                               _lib.stream_ptr(self.device)))
+                if rot:
+                    _lib.check(self.lib.da_train_backward_rot(C.byref(self.w), C.byref(self.gw), C.byref(g), _lib.ptr(x), _lib.ptr(t),
+                                                              _lib.ptr(d_out), _lib.ptr(d_out_rot), _lib.ptr(d_feats), _lib.ptr(ws), ws.numel(),
+                                                              mma, stage, _lib.stream_ptr(self.device)))
+                else:
+                    _lib.check(bwd(C.byref(self.w), C.byref(self.gw), C.byref(g), _lib.ptr(x), _lib.ptr(t),
+                                   _lib.ptr(d_out), _lib.ptr(d_feats), _lib.ptr(ws), ws.numel(), mma, stage,
+                                   _lib.stream_ptr(self.device)))
                 if stage == _lib.TRAIN_BWD_EARLY and overlap:
                     self._exchange_early()
         if not attached:
@@ -339,6 +371,29 @@ class DenoiserTrainFn(torch.autograd.Function):
         x, t = ctx.saved_tensors
         d_feats = ctx.eng.backward(ctx.plan, x, t, d_out, ctx.want_dfeats)
         return None, None, None, None, d_feats, torch.zeros(ctx.anchor_shape, dtype=torch.float32, device=d_out.device)
+
+
+class DenoiserTrainFn2(torch.autograd.Function):
+    """``DenoiserTrainFn`` for the two-headed ``Eff_GAT_Discrete_ROT``: (logits, rot_logits) = forward_with_feats(idx, t, feats), the
+    backward one da_train_backward_rot call over both heads' gradients.  A head whose output took no part in the loss hands no gradient
+    on: the position head's products are then skipped (only_rotation), a missing rotation gradient counts as zeros.  Same anchor
+    mechanism, same one-forward-then-its-backward rule."""
+
+    @staticmethod
+    def forward(ctx, eng, plan, x, t, feats, anchor):
+        out, out_rot = eng.forward(plan, x, t, feats)
+        ctx.eng, ctx.plan = eng, plan
+        ctx.want_dfeats = bool(feats.requires_grad)
+        ctx.save_for_backward(x, t)
+        ctx.anchor_shape = anchor.shape
+        ctx.set_materialize_grads(False)
+        return out, out_rot
+
+    @staticmethod
+    def backward(ctx, d_out, d_out_rot):
+        x, t = ctx.saved_tensors
+        d_feats = ctx.eng.backward(ctx.plan, x, t, d_out, ctx.want_dfeats, d_out_rot=d_out_rot)
+        return None, None, None, None, d_feats, torch.zeros(ctx.anchor_shape, dtype=torch.float32, device=x.device)
 
 
 class FusedAdafactor(torch.optim.Optimizer):

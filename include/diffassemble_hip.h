@@ -684,6 +684,49 @@ int da_train_backward_idx(const da_weights *w, const da_weights *grads, const da
                           const int64_t *t, const float *d_logits, float *d_feats, void *workspace, size_t workspace_bytes,
                           int mma_precision, int stage, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Training of the discrete position + rotation model (additive to ABI 19): p_losses of spatial_diffusion_discrete_rot.py
+ * (:161-279).  Two D3PM processes with the uniform transition, K positions and 4 quarter turns; the formulas are those of the
+ * section above, evaluated once with K and once with 4.  The network reads neither rot_noisy nor rot_start: they enter the loss.
+ *
+ * da_d3pm_q_sample_rot: both noisings in one launch, one wave per piece.  The position half is da_d3pm_q_sample (same
+ *   expressions, same DA_D3PM_DRAW_TRAINING stream: bit-identical for the same seed); the rotation half is the same formula
+ *   over four classes (rot_start taken mod 4), its uniforms noise_rot [n, 4] or drawn in the domain DA_D3PM_DRAW_TRAINING_ROT
+ *   (its own counter word, flat element r * 4 + k; da_d3pm_noise_ex writes that stream out).  x_noisy == NULL skips the
+ *   position half (only_rotation; x_start / noise_x are then not read).  A missing noise buffer needs `seed`.
+ *
+ * da_d3pm_rot_loss: both heads' loss AND its gradient with respect to both logits (for unit upstream gradients), per piece:
+ *   vb_row and ce_row of da_d3pm_loss for (logits, x_start, x_t) with K classes and for (rot_logits, rot_start, rot_t) with 4.
+ *   Label smoothing as the reference has it: kind _CE smooths neither cross entropy, kind _HYBRID smooths the position head's
+ *   (label_smoothing 1e-2, y = 0.99 e_{x_start} + 0.01 / K) and not the rotation head's.
+ *     x_loss, rot_loss = mean vb_row (_VB) | mean ce_row (_CE) | lambda mean ce_row + mean vb_row (_HYBRID), each from its head
+ *   loss [6] = {x_loss, rot_loss, mean x_vb, mean x_ce, mean rot_vb, mean rot_ce} (a term the kind does not use reads 0);
+ *   d_logits [n, K] = d x_loss / d logits, d_rot_logits [n, 4] = d rot_loss / d rot_logits (the 1 / n and the weights applied);
+ *   row_terms [n, 4] = {x_vb, x_ce, rot_vb, rot_ce} feeds the finishing reduction: one workgroup, fixed order, no float atomics.
+ *   logits == NULL (only_rotation): the position half is skipped, d_logits is not touched, loss[0], loss[2], loss[3] read 0
+ *   (x_start / x_t / d_logits may then be NULL).                                                                            */
+enum { DA_D3PM_DRAW_TRAINING_ROT = 3 };          /* da_d3pm_noise_ex: the rotation half of the training-side noising, [n, 4] */
+int da_d3pm_q_sample_rot(const da_schedule *s, int n, int K, const int32_t *x_start, const int32_t *rot_start, const int64_t *t,
+                         const float *noise_x, const float *noise_rot, const uint64_t *seed, int iteration, int32_t *x_noisy,
+                         int32_t *rot_noisy, void *stream);
+int da_d3pm_rot_loss(const da_schedule *s, int n, int K, int kind, float lambda, const float *logits, const float *rot_logits,
+                     const int32_t *x_start, const int32_t *x_t, const int32_t *rot_start, const int32_t *rot_t, const int64_t *t,
+                     float *loss, float *d_logits, float *d_rot_logits, float *row_terms, void *stream);
+/* The two-head denoiser's training forward / backward.  w->variant must be DA_VARIANT_DISCRETE_ROT: everything of
+ * DA_VARIANT_DISCRETE plus head_r_w0 / head_r_b0 = final_mlp_rot.0 [32, D] / [32] and head_r_w1 / head_r_b1 = final_mlp_rot.2
+ * [4, 32] / [4].  The first layer of both heads is ONE [64, D] product forward and ONE dX / dW product backward, so
+ * head_w0 | head_r_w0 and head_b0 | head_r_b0 must each be one gap-free slot in that order (weights, then biases), in `w` and in
+ * `grads`.  logits [n_real, K] come from columns 0..31 of the post-GELU rows, rot_logits [n_real, 4] from columns 32..63, both
+ * fp32 in both mma_precision modes; they and their gradients are the caller's buffers.  d_logits == NULL (only_rotation) skips
+ * the position head's second-layer products and leaves the gradient slots of final_mlp.2 untouched (final_mlp.0's receive zero).
+ * The float-pose and the _idx entries reject this variant, these reject every other one, before anything is launched.
+ * DA_TRAIN_BWD_EARLY / _LATE keep their meaning (both heads early); workspace size from da_train_workspace_bytes_ex.       */
+int da_train_forward_rot(const da_weights *w, const da_graph *g, const int32_t *idx, const int64_t *t, const float *feats,
+                         float *logits, float *rot_logits, void *workspace, size_t workspace_bytes, int mma_precision, void *stream);
+int da_train_backward_rot(const da_weights *w, const da_weights *grads, const da_graph *g, const int32_t *idx, const int64_t *t,
+                          const float *d_logits, const float *d_rot_logits, float *d_feats, void *workspace, size_t workspace_bytes,
+                          int mma_precision, int stage, void *stream);
+
 /* The 3D model's training glue (additive to ABI 19):
  *   da_head3d_backward  the pose head's backward on its own: pre [n, 6] = [r | t] (what the head's second Linear layers
  *                       produce), d_out [n, 7] the gradient of [q | t], q = normalize(matrix_to_quaternion(exp(skew(r))))
