@@ -9,23 +9,9 @@
 // (b) retire that row and column, (c) rows whose cached minimum was the retired column rescan their free
 // columns -- a wave per row.  Ties resolve like the reference's `dist[mask].min()`: first in row-major order
 // (smallest row, then smallest column).  Distances are sqrt(dx*dx + dy*dy) in fp32, never materialised.
-#include "da_common.h"
+#include "da_assign_common.h"      // dist2, lexmin
 
 namespace da {
-
-__device__ __forceinline__ float dist2(const float *a, const float *b) {
-    const float dx = a[0] - b[0], dy = a[1] - b[1];
-    const float d = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
-    // a diverged sample (NaN / Inf poses) must still be assignable: +inf is the "retired" marker of rmin and a NaN
-    // never wins a comparison, so non-finite distances rank as the largest finite value (the reference returns
-    // some wrong assignment in that case; here the row simply goes last, and nothing indexes out of LDS)
-    return d <= 3.402823466e38f ? d : 3.402823466e38f;
-}
-
-// lexicographic (value, index) minimum
-__device__ __forceinline__ void lexmin(float &v, int &i, float v2, int i2) {
-    if (v2 < v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-}
 
 __global__ __launch_bounds__(1024) void k_greedy_assign(const float *__restrict__ pos1, int ld1, const float *__restrict__ pos2,
                                                         int ld2, const int32_t *__restrict__ ptr1,

@@ -18,7 +18,6 @@ Differences from the reference, on purpose:
 """
 import enum
 import os
-import math
 from functools import partial
 from typing import Any
 
@@ -439,48 +438,24 @@ class GNN_Diffusion(LightningModule):
     @torch.no_grad()
     def _eval_step(self, batch, batch_idx):
         """validation_step / test_step, spatial_diffusion.py:775-903,915-: sampling loop, greedy
-        assignment of predicted positions to the grid, puzzle / piece accuracy."""
+        assignment of predicted positions to the grid, puzzle / piece accuracy.  The whole Batch is scored by one
+        ``score2d.batch_scores`` call (da_score2d); the metrics are updated from its one host copy."""
         imgs, _ = self.p_sample_loop(batch.x.shape, batch.patches, batch.edge_index, batch=batch.batch,
                                      patch_feats=getattr(batch, "patch_feats", None), expander=self._expander_of(batch))
         img = imgs[-1]
-        G = int(batch.batch.max()) + 1
-        dims = batch.patches_dim.tolist()
-        grids = []
-        for i in range(G):
-            y = torch.linspace(-1, 1, dims[i][0], device=self.device)
-            x = torch.linspace(-1, 1, dims[i][1], device=self.device)
-            grids.append(torch.stack(torch.meshgrid(x, y, indexing="xy"), -1).reshape(-1, 2))
-        counts = torch.bincount(batch.batch, minlength=G)
-        ptr = torch.zeros(G + 1, dtype=torch.int32, device=self.device)
-        ptr[1:] = torch.cumsum(counts, 0)
-        batched = img.is_cuda and all(g.shape[0] == int(c) for g, c in zip(grids, counts))
-        if batched:                                        # both assignments of every puzzle: two launches
-            from ..engine import greedy_assign
-            grid_all = torch.cat(grids)
-            gt_all = greedy_assign(batch.x[:, :2], grid_all, ptr, ptr)
-            pred_all = greedy_assign(img[:, :2], grid_all, ptr, ptr)
-        for i in range(G):
-            idx = torch.where(batch.batch == i)[0]
-            n_patches = dims[i]
-            if batched:
-                lo, hi = int(ptr[i]), int(ptr[i + 1])
-                gt_ass, pred_ass = gt_all[lo:hi], pred_all[lo:hi]
-            else:
-                gt_ass = greedy_cost_assignment(batch.x[idx, :2], grids[i])
-                pred_ass = greedy_cost_assignment(img[idx, :2], grids[i])
-            gt_ass = gt_ass[torch.sort(gt_ass[:, 0])[1]]
-            pred_ass = pred_ass[torch.sort(pred_ass[:, 0])[1]]
-            piece_accuracy = (gt_ass[:, 1] == pred_ass[:, 1]).to(self.device)
-            correct = bool(piece_accuracy.all())
-            if self.rotation:
-                rot_correct = torch.cosine_similarity(img[idx, 2:], batch.x[idx, 2:]) > math.cos(math.pi / 4)
-                correct = correct and bool(rot_correct.all())
-                piece_accuracy = rot_correct * piece_accuracy
-            if hasattr(self, "metrics"):
-                key = f"{tuple(n_patches)}"
-                for name, val in ((f"{key}_acc", float(correct)), (f"{key}__piece_acc", piece_accuracy.float()),
-                                  (f"{key}_nImages", 1), ("overall_acc", float(correct)),
-                                  ("overall__piece_acc", piece_accuracy.float()), ("overall_nImages", 1)):
+        from ..score2d import batch_scores
+        piece_ok, correct, sizes = batch_scores(img, batch.x, batch.patches_dim, batch=batch.batch, rotation=bool(self.rotation),
+                                                return_sizes=True)
+        if hasattr(self, "metrics"):
+            piece_ok, correct, sizes = piece_ok.float(), correct.tolist(), sizes.tolist()
+            lo = 0
+            for i, (flags, rows, cols) in enumerate(sizes):
+                key = f"{(rows, cols)}"
+                piece_accuracy = piece_ok[lo:lo + flags]
+                lo += flags
+                for name, val in ((f"{key}_acc", float(correct[i])), (f"{key}__piece_acc", piece_accuracy),
+                                  (f"{key}_nImages", 1), ("overall_acc", float(correct[i])),
+                                  ("overall__piece_acc", piece_accuracy), ("overall_nImages", 1)):
                     if name in self.metrics:
                         self.metrics[name].update(val)
         return img

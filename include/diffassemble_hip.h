@@ -810,6 +810,24 @@ int da_greedy_assign(int n_puzzles, const float *pos1, int ld1, const float *pos
                      void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Puzzle and piece accuracy of a whole 2D Batch in ONE launch, one workgroup per puzzle, no host sync.
+ * Replaces the per-puzzle scoring of validation_step / test_step (spatial_diffusion.py:775-856, 915-955): two
+ * greedy_cost_assignment calls per puzzle (ground truth -> grid, prediction -> grid), the two sorts by row, the comparison
+ * of the assigned cells and, with rotation, the cosine test of columns 2..3.  Puzzle g owns rows ptr_piece[g] ..
+ * ptr_piece[g + 1] of pred and gt (row strides ld_pred / ld_gt floats: x, y, then cos, sin) and rows ptr_cell[g] ..
+ * ptr_cell[g + 1] of grid (its cell centres; x and y in the first two columns).  Both assignments are da_greedy_assign's,
+ * bit for bit: the same fp32 distance, ties -> first in row-major order (smallest piece, then smallest cell), like the
+ * reference.  PRECONDITION n_g <= m_g (pieces <= cells) for every puzzle: max_n > max_m is refused here; a puzzle that
+ * breaks it inside a ragged Batch gets per_puzzle[g][0] = -1 and none of its other outputs is written.
+ * cell_pred / cell_gt [N]: the cell (local index) assigned to each piece, either may be NULL; piece_ok [N] = same cell (and,
+ * with rotation, cosine_similarity(pred[i, 2:4], gt[i, 2:4]) > (float)cos(pi / 4), each norm clamped at 1e-8, NaN -> 0);
+ * per_puzzle [n_puzzles, 4] = (all_correct, n_ok, n_pos_ok, n_rot_ok).  No allocation, no atomics, launched on `stream`.
+ * ------------------------------------------------------------------------------------- */
+int da_score2d(int n_puzzles, const float *pred, int ld_pred, const float *gt, int ld_gt, const float *grid, int ld_grid,
+               const int32_t *ptr_piece, const int32_t *ptr_cell, int max_n, int max_m, int rotation,
+               int32_t *cell_pred, int32_t *cell_gt, uint8_t *piece_ok, int32_t *per_puzzle, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * 2D piece encoder: the P4 group-equivariant ResNet-18 the reference builds
  * for model='resnet18equiv', eval-mode BatchNorm.  Replaces Eff_GAT.visual_features
  * (backbones/efficient_gat.py:149-189) = normalise + ResNet.forward (backbones/resnet_equivariant.py:
