@@ -23,13 +23,15 @@ ACT_NONE, ACT_GELU, ACT_LEAKY02 = 0, 1, 2
 CONV_Q_PRESCALED, CONV_FOLDED_V32 = 1, 2
 CONV_X_FM, CONV_OUT_FM = 4, 8          # da_conv_dense_ex: x is / out is written fragment-major over the padded slots (DA_CONV_X_FM / DA_CONV_OUT_FM)
 FOLD_ATTN_PROJ, FOLD_X_FM = 64, 128    # da_config.disable_folds: set = keep the projection kernel / keep the hidden layers' rows row-major between them
+FOLD_LAST_QPROJ = 256                  # ... set = the folded last layer's projection kernel keeps its Q columns (DA_FOLD_LAST_QPROJ)
 TRAIN_MMA_FP32, TRAIN_MMA_BF16 = 0, 1
 TRAIN_BWD_ALL, TRAIN_BWD_EARLY, TRAIN_BWD_LATE = 0, 1, 2
 D3PM_DRAW_SAMPLING, D3PM_DRAW_TRAINING, D3PM_DRAW_SAMPLING_ROT, D3PM_DRAW_TRAINING_ROT = 0, 1, 2, 3
 D3PM_LOSS = {"vb": 0, "cross_entropy": 1, "hybrid": 2}
 DBG_COUNTERS = ("opt_gen_workgroups", "dense_fast_exits", "dual_gen_slabs", "opt_masked_gen_workgroups")          # fallback events (indices 0 .. 3)
 DBG_LAUNCH_COUNTERS = {"resident_launches": 4, "virtual_rows_in_launch": 5,           # which kernel took a layer (DA_DBG_RES_LAUNCHES, DA_DBG_VIRT_IN_LAUNCH,
-                       "resident_projection_launches": 6, "resident_fm_input_launches": 7}    # DA_DBG_RES_PROJ_LAUNCHES, DA_DBG_RES_FM_LAUNCHES)
+                       "resident_projection_launches": 6, "resident_fm_input_launches": 7,     # DA_DBG_RES_PROJ_LAUNCHES, DA_DBG_RES_FM_LAUNCHES,
+                       "last_qproj_launches": 8}                                               # DA_DBG_LAST_QPROJ_LAUNCHES)
 PROF_CLASSES = ("embed", "linear_mlp", "linear_qkvs", "attn_hidden", "attn_last", "head", "update", "conv_fused")
 
 _fp = C.c_void_p        # device pointers travel as integers

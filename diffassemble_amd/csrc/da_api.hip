@@ -2,6 +2,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
 
 #include <utility>
 #include <vector>
@@ -105,6 +106,12 @@ struct da_denoiser {
     void *virt_qkvs = nullptr;        // exophormer: [V, 4*HC0] act dtype = virt_emb . Wcat0^T + bcat0 (constant per checkpoint)
     void *conv0c_wd = nullptr, *virt_qkvs_d = nullptr;      // their dense-path variants (Q pre-scaled, see ConvW)
     void *conv0c_wdp = nullptr, *convLf_wp = nullptr;       // conv0c_wd / convLf_w packed for the row-panel kernel (see ConvW::wdp)
+    // disable_folds bit 256 (DA_FOLD_LAST_QPROJ) was clear when this denoiser was created: the folded last layer of complete graphs projects Q in the prologue
+    // of its attention kernel (k_attn_optt<144, true, false, .., 8192>), the projection kernel in front of it writes the K | V' columns only
+    bool last_qproj = false;
+    long owner_pid = 0;               // the process that created this denoiser: a forked child holds a copy of the handle but no HIP context (da_denoiser_destroy)
+    void *convLf_wp_kv = nullptr;     // rows HC .. of convLf_w (K | V') packed for the row-panel kernel
+    void *convLf_wq = nullptr;        // pack_w_qlast image of rows 0 .. HC - 1 (Q)
     void *conv0c_wqs = nullptr;                             // conv0c_wd's per-head fragments (see ConvW::wqs)
     bool attn_qsf = false;            // disable_folds bit 64 was clear when this denoiser was created: the wqs images exist, hidden layers of large complete
                                       // graphs are projected by their attention kernel (a later da_config_set changes neither)
@@ -420,13 +427,24 @@ static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const
             QkvScatter qs;
             qs.HC = c.hc; qs.C = c.C; qs.Cv = 32; qs.n_pad = g->n_pad; qs.row_map = g->row_map;
             qs.Q = w.dq; qs.K = w.dk; qs.Vt = w.dvt; qs.S = nullptr;
+            // complete graphs (disable_folds bit 256 clear at creation): the K | V' columns only -- Q is projected by the attention kernel, per 32-query slab,
+            // in its prologue, and never exists in memory (45 % of this launch's stores, and the attention kernel's reads of them).  Hybrid graphs keep the
+            // three-block launch and the masked kernel.
+            const bool lq = d->last_qproj && !g->hybrid && n == nr && !x_fm &&
+                            attn_last_qproj_applicable(prec, d->heads, c.C, c.din, g->n_pad, d->q_prescaled);
+            if (lq) qs.col0 = c.hc;
             rc = timed(d, DA_PROF_LINEAR_QKVS, st, [&] {
+                if (lq)
+                    return launch_gemm_mfma(prec, n, c.din, c.hc + d->heads * 32, xin, ldx, (const char *)d->convLf_w + (size_t)c.hc * c.din * esize(prec),
+                                            d->convLf_b + c.hc, DA_ACT_NONE, nullptr, nullptr, 0, &qs, st, 0, nullptr, d->convLf_wp_kv);
                 return launch_gemm_mfma(prec, n, c.din, 2 * c.hc + d->heads * 32, xin, ldx, d->convLf_w, d->convLf_b, DA_ACT_NONE,
                                         nullptr, nullptr, 0, &qs, st, 0, nullptr, d->convLf_wp); });
             if (rc > 0) return rc;
+            DA_REQUIRE(rc == 0 || !lq, "da_denoiser_forward: no projection kernel took the last layer's K | V' columns");
             if (rc == 0) {
                 DenseLayout L;
                 L.Q = w.dq; L.K = w.dk; L.Vt = w.dvt; L.S = nullptr; L.n_pad = g->n_pad; L.q_prescaled = d->q_prescaled;
+                if (lq) { L.Q = nullptr; L.x = xin; L.ldx = ldx; L.kin = c.din; L.wqs = d->convLf_wq; L.bias = d->convLf_b; }
                 DenseFold fo;
                 fo.cv = 32; fo.out = disc ? (void *)disc->pz : w.pz; fo.n_rows = nr;
                 // hybrid graphs: adjacency-masked, remainder edges of the real rows folded in the epilogue; the
@@ -770,6 +788,7 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
     }
     hipStream_t st = (hipStream_t)stream;
     da_denoiser *d = new da_denoiser();
+    d->owner_pid = (long)getpid();
     d->prec = precision; d->variant = w->variant; d->arch = w->arch; d->steps = w->steps; d->c_in = w->c_in;
     d->c_out = w->c_out; d->F = w->feat_dim; d->D = w->feat_dim + 64; d->hidden = w->hidden; d->heads = w->heads;
     d->n_layers = w->n_layers; d->V = w->arch == DA_ARCH_EXOPHORMER ? w->virt_nodes : 0;
@@ -994,6 +1013,12 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
                 }
                 d->convLf_w = pack(lw, (size_t)nf * dinL);
                 d->convLf_wp = pack_panel(d->convLf_w, dinL, nf);
+                d->last_qproj = attn_last_qproj_enabled() && precision == DA_PREC_BF16 && H == 8 && dinL == 256 && d->q_prescaled && d->convLf_w && !mfma_disabled();
+                if (d->last_qproj) {
+                    d->convLf_wp_kv = pack_panel((const char *)d->convLf_w + blk * s, dinL, nf - hcL);
+                    d->convLf_wq = alloc(w_qlast_bytes(H, CL, dinL));
+                    if (!d->convLf_wq || pack_w_qlast(H, CL, dinL, d->convLf_w, d->convLf_wq, st)) return fail(2);
+                }
                 d->skipc_w = pack(sw, (size_t)32 * dinL);
                 if (rc) return fail(rc);
                 d->lastfold = true;
@@ -1032,6 +1057,9 @@ int da_denoiser_flags(const da_denoiser *d) {
 
 void da_denoiser_destroy(da_denoiser *d) {
     if (!d) return;
+    // A forked child (multiprocessing's default start method) inherits the handle, and its garbage collector may drop it: the graphs, streams and
+    // allocations belong to the parent's HIP context, and destroying them from the child faults.  The child gives up its copy of the host record only.
+    if (d->owner_pid != (long)getpid()) { delete d; return; }
     for (hipEvent_t e : d->prof_ev) (void)hipEventDestroy(e);
     for (auto &e : d->loops) (void)hipGraphExecDestroy(e.exec);
     if (d->cap_stream) (void)hipStreamDestroy(d->cap_stream);
@@ -1506,7 +1534,9 @@ int da_sample_loop_rot(da_denoiser *d, const da_graph *g, const da_schedule *s, 
 size_t da_attn_dense_scratch_bytes(int prec, const da_graph *g, int heads, int C) {
     if (!g) return 0;
     const size_t s = esize(prec), hc = (size_t)heads * C;
-    return 3 * align_up(((size_t)g->n_pad + 64) * hc * s, 256) + align_up(((size_t)g->n_nodes + 64) * hc * s, 256);
+    // (+ behind the four regions, for the folded C = 144 layer: room for the Q weights' pack_w_qlast image, da_conv_dense_ex)
+    return 3 * align_up(((size_t)g->n_pad + 64) * hc * s, 256) + align_up(((size_t)g->n_nodes + 64) * hc * s, 256) +
+           (heads == 8 && C == 144 ? w_qlast_bytes(heads, C, 256) : 0);
 }
 
 int da_conv_dense(int prec, const da_graph *g, int heads, int C, int Din, const void *x, const void *w,
@@ -1562,15 +1592,25 @@ int da_conv_dense_ex(int prec, const da_graph *g, int heads, int C, int Din, con
     // fragment-major rows are a layout of THAT kernel's prologue and epilogue: no other path reads or writes it
     DA_REQUIRE(qsf || !(flags & DA_CONV_X_FM), "da_conv_dense_ex: DA_CONV_X_FM on a call that does not take the projection in the attention kernel");
     DA_REQUIRE(qsf || !(flags & DA_CONV_OUT_FM), "da_conv_dense_ex: DA_CONV_OUT_FM on a call that does not take the projection in the attention kernel");
+    // the folded last layer of complete graphs as the sampling loop runs it (disable_folds bit 256 clear): the K | V' columns only, Q projected by the
+    // attention kernel in its prologue -- the scratch's Q region is neither written nor read; the Q weights' fragment image goes behind the four regions
+    const bool lq = folded && attn_last_qproj_enabled() && !g->hybrid && g->n_nodes == g->n_real && b &&
+                    attn_last_qproj_applicable(prec, heads, C, Din, g->n_pad, (flags & DA_CONV_Q_PRESCALED) ? 1 : 0);
+    void *wq_last = base + 3 * hb + align_up(((size_t)g->n_nodes + 64) * hc * s, 256);
     int rc = 0;
     if (qsf) {
         if ((rc = pack_w_qs(heads, Din, (int)hc, w, wq_img, st))) return rc;
+    } else if (lq) {
+        if ((rc = pack_w_qlast(heads, C, Din, w, wq_last, st))) return rc;
+        qs.col0 = (int)hc;
+        rc = launch_gemm_mfma(prec, g->n_nodes, Din, nout - (int)hc, x, Din, (const char *)w + hc * (size_t)Din * s, b + hc, DA_ACT_NONE, nullptr, nullptr, 0, &qs, st);
     } else
     rc = launch_gemm_mfma(prec, g->n_nodes, Din, nout, x, Din, w, b, DA_ACT_NONE, nullptr, nullptr, 0, &qs, st);
     DA_REQUIRE(rc == 0, "da_conv_dense_ex: projection shape (Din=%d, Nout=%d) not supported by the MFMA kernels", Din, nout);
     DenseLayout L;
     L.Q = qs.Q; L.K = qs.K; L.Vt = qs.Vt; L.S = qs.S; L.n_pad = g->n_pad; L.q_prescaled = (flags & DA_CONV_Q_PRESCALED) ? 1 : 0;
     if (qsf) { L.x = x; L.ldx = Din; L.kin = Din; L.wqs = wq_img; L.bias = b; L.x_fm = (flags & DA_CONV_X_FM) != 0; L.out_fm = (flags & DA_CONV_OUT_FM) != 0; }
+    if (lq) { L.Q = nullptr; L.x = x; L.ldx = Din; L.kin = Din; L.wqs = wq_last; L.bias = b; }
     DenseFold fo;
     fo.cv = 32; fo.out = out; fo.n_rows = g->n_real;
     const DenseMask mk = dense_mask_of(g);
@@ -1581,7 +1621,8 @@ int da_conv_dense_ex(int prec, const da_graph *g, int heads, int C, int Din, con
 }
 
 int da_debug_counters(int64_t *out, int n, int reset) {
-    DA_REQUIRE(out && n >= DA_DBG_NCOUNTERS, "da_debug_counters: need room for %d counters", DA_DBG_NCOUNTERS);
+    // (counters are only ever ADDED behind the first eight: a caller compiled against fewer gets the ones it has room for)
+    DA_REQUIRE(out && n >= 8, "da_debug_counters: need room for 8 counters (%d exist)", DA_DBG_NCOUNTERS);
     unsigned long long a[4] = {0, 0, 0, 0}, b2[2] = {0, 0};
     int rc;
     if ((rc = da::attn_dense_counters(a, reset))) return rc;
@@ -1597,6 +1638,8 @@ int da_debug_counters(int64_t *out, int n, int reset) {
     out[DA_DBG_RES_PROJ_LAUNCHES] = (int64_t)da::attn_res_qsf_launches(reset);
     out[DA_DBG_RES_FM_LAUNCHES] = (int64_t)da::attn_res_fm_launches(reset);
     out[DA_DBG_VIRT_IN_LAUNCH] = (int64_t)da::attn_virt_launches(reset);
+    const int64_t lq = (int64_t)da::attn_last_qproj_launches(reset);
+    if (n > DA_DBG_LAST_QPROJ_LAUNCHES) out[DA_DBG_LAST_QPROJ_LAUNCHES] = lq;
     return 0;
 }
 

@@ -903,6 +903,7 @@ int launch_attn_dense(int prec, const DenseLayout &L, int heads, int C, int n_gr
             const int ro = launch_attn_opt(p, C, st);
             if (ro >= 0) return ro;                        // (-1: shape not covered, e.g. masked graphs beyond 4096 pieces)
         }
+        DA_REQUIRE(!p.x, "launch_attn_dense: Q in the prologue requested for a folded layer the optimistic kernel does not take");
         if (mk) return prec == DA_PREC_BF16 ? launch_tcm<bf16_t, 144, true, 32>(p, st) : launch_tcm<float, 144, true, 32>(p, st);
         return prec == DA_PREC_BF16 ? launch_tcm<bf16_t, 144, false, 32>(p, st) : launch_tcm<float, 144, false, 32>(p, st);
     }
@@ -930,6 +931,16 @@ bool attn_qsf_applicable(int prec, int heads, int C, int kin, int n_graphs, int 
     if ((size_t)C * (size_t)n_pad * 2 >= ((size_t)1 << 31)) return false;
     return attn_res_qsf_shape_ok(max_graph_nodes, n_pad, n_graphs, kin);
 }
+// The conditions under which launch_attn_dense hands an un-masked folded last layer with L.x set to k_attn_optt<144, true, false, .., 8192> (Q projected in
+// the attention kernel's prologue; the caller then launches the K | V' columns of the projection only).  Same contract as attn_qsf_applicable.
+bool attn_last_qproj_shape_ok(int heads, int C, int kin);          // da_attn_opt.hip
+bool attn_last_qproj_applicable(int prec, int heads, int C, int kin, int n_pad, int q_prescaled) {
+    if (prec != DA_PREC_BF16 || !q_prescaled || !attn_opt_env() || !attn_opt_last_env() || !DA_XENV("DA_ATTN_LAST_FAST", 1)) return false;
+    if (DA_XENV("DA_ATTN_NO_FAST", 0) || attn_dual_env() DA_ATTN_DBG(|| DA_XENV_LIVE("DA_ATTN_DEBUG") || DA_XENV_LIVE("DA_ATTN_PROF_PTR"))) return false;
+    if ((size_t)C * (size_t)n_pad * 2 >= ((size_t)1 << 31)) return false;
+    return attn_last_qproj_shape_ok(heads, C, kin);
+}
+bool attn_last_qproj_enabled() { return !(cfg().disable_folds & DA_FOLD_LAST_QPROJ); }
 bool attn_qsf_enabled() {          // (experiments build: DA_ATTN_RES_QSF=0 / 1 overrides the switch)
     const int x = DA_XENV("DA_ATTN_RES_QSF", -1);
     return x < 0 ? !(cfg().disable_folds & DA_FOLD_ATTN_PROJ) : x != 0;

@@ -238,8 +238,156 @@ __global__ __launch_bounds__(64 * NWV, MINB) void k_attn_optt(AttnDenseParams p)
     const int HC = p.H * C;
     const size_t np = (size_t)p.n_pad;
 
+    // VAR bit 8192 (the un-masked folded last layer, p.x set; da_config.disable_folds bit 256 clear): THE LAYER'S Q IN THE PROLOGUE.  No Q row is ever
+    // written or read: the projection kernel in front of this launch holds the K | V' columns only (QkvScatter::col0), and every wave projects the Q
+    // fragments of its own 32-query slab here, on the matrix pipe: Q^T (channel x query) = W_h x^T, five 32-channel blocks (144 channels; the upper
+    // half of the fifth block multiplies zero rows), each one 16-step chain of the projection kernels' instruction over the slab's x rows (B operand:
+    // lane (query, half), k-step s: x[query][16 s + 8 half .. + 7]; 32-byte pieces of 32 rows, read once per wave).  The A operands come from the
+    // head's pack_w_qlast image -- MFMA row a = channel pi(a), bits 2 and 3 swapped, so accumulator registers 8 t .. 8 t + 7 of a lane are channels
+    // 16 t + 8 half .. + 7: exactly the 16-byte chunk qf[2 b + t] the key loop wants.  Same chain, bias behind the reduction, same pre-scale (it sits in W and the
+    // bias), same rounding as the projection kernels: the fragments are the Q rows of the two-kernel path bit for bit.  A slab's rows behind its
+    // graph repeat the graph's last row (nothing of them is stored).  The running-max re-run below reuses qf as it always did.
+    constexpr bool QPROJ = (VAR & 8192) != 0;
+    static_assert(!QPROJ || (C == 144 && FOLD && !MASKED), "Q in the prologue: the un-masked folded last layer");
+    // + bit 16384: the weight fragments STAGED through the ring's LDS, which is idle until the key loop starts -- the four waves of a workgroup multiply
+    // the same 80 KB, and as direct loads every wave pulls them through the vector memory path on its own (as much L2 -> CU traffic again as the
+    // kernel's whole K | V stream).  One 16 KB block (sixteen k-steps) per buffer, three buffers, filled by LDS-DMA, four k-steps per wave: blocks 0 .. 2
+    // are requested up front, block b + 2 behind the barrier that says block b has landed (which also says everybody is done with block b - 1, whose
+    // buffer it takes).  Measured (profiles/r13/NOTES.md, interleaved pairs against the two-kernel step): direct loads -8 us per step, staged -25 us; the
+    // product build holds the staged form only.  Waves without a slab stage their share and keep the barriers.  The image in LDS is the image in memory: k-step s of a block
+    // is the KB at s * 1024, a lane's fragment the 16 bytes at lane * 16 (conflict-free ds_read_b128).
+    constexpr bool QSTG = QPROJ && (VAR & 16384) != 0;
+    static_assert(!QSTG || NWV == 4, "staged weights: four k-steps of a block per wave");
     u32x4 qf[CF::NCH];
-    {
+    if constexpr (QSTG) {
+        constexpr int KS = 16, NB = (C + 31) / 32, WBUF = KS * 1024, NBUF = 3, LPF = 3;
+        const unsigned char *wsrc = (const unsigned char *)p.wqs + (size_t)h * (NB * WBUF);
+        const unsigned ldsq = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem;
+        const unsigned lo16 = (unsigned)lane * 16u;
+        auto stage = [&](int b) {          // this wave's four k-steps of block b -> buffer b % NBUF
+#pragma unroll
+            for (int k = 0; k < KS / NW; ++k) {
+                const int s = wid + NW * k;
+                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(ldsq + (unsigned)((b % NBUF) * WBUF + s * 1024)), "v"(lo16),
+                             "s"(wsrc + (size_t)(b * KS + s) * 1024)
+                             : "memory");
+            }
+        };
+        u32x4 xq[KS];
+        float bv[(C + 63) / 64];
+        // (bias words: this wave's own 768 B behind the weight buffers, see the direct form below)
+        float *bq = (float *)(smem + (NST * MSTAGE + 64 > NBUF * WBUF ? NST * MSTAGE + 64 : NBUF * WBUF)) + wid * 192;
+        // Every vector-memory operation of this prologue is issued by hand, oldest first: bias words, x rows, DMA -- a load the compiler tracks gets ITS
+        // wait (counted without the DMA it cannot see: vmcnt(0) at the end of every chain, i.e. a wait for the blocks just requested).  The one wait
+        // that makes the registers valid is block 0's below, which carries them as operands.  (Waves without a slab load their clamped row too.)
+        {
+            const unsigned char *xrow = (const unsigned char *)p.x + ((size_t)(node0 + min(q0 + i, n_g - 1)) * (size_t)p.ldx + 8 * half) * 2;
+#pragma unroll
+            for (int k = 0; k < (C + 63) / 64; ++k)
+                asm volatile("global_load_dword %0, %1, off" : "=v"(bv[k]) : "v"(p.bias_q + h * C + min(lane + 64 * k, C - 1)) : "memory");
+#pragma unroll
+            for (int s = 0; s < KS; ++s) asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(xq[s]) : "v"(xrow), "n"(s * 32) : "memory");
+        }
+        stage(0); stage(1); stage(2);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            // this wave's share of block b has landed: what may stay in flight are its shares of the blocks requested behind it (and nothing else:
+            // the x rows and bias words are older than every DMA of this wave)
+            if (b == 0) {
+                static_assert(KS == 16 && (C + 63) / 64 == 3, "the operand list below");
+                asm volatile("s_waitcnt vmcnt(8)"
+                             : "+v"(xq[0]), "+v"(xq[1]), "+v"(xq[2]), "+v"(xq[3]), "+v"(xq[4]), "+v"(xq[5]), "+v"(xq[6]), "+v"(xq[7]), "+v"(xq[8]), "+v"(xq[9]),
+                               "+v"(xq[10]), "+v"(xq[11]), "+v"(xq[12]), "+v"(xq[13]), "+v"(xq[14]), "+v"(xq[15]), "+v"(bv[0]), "+v"(bv[1]), "+v"(bv[2])
+                             :
+                             : "memory");
+#pragma unroll
+                for (int k = 0; k < (C + 63) / 64; ++k) bq[lane + 64 * k] = bv[k];
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                bq += 8 * half;
+            } else if (b == NB - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            if (b >= 1 && b + 2 < NB) stage(b + 2);
+            if (wave_on) {
+                const unsigned char *wb = smem + (b % NBUF) * WBUF + lo16;
+                f32x16 a;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) a[r] = 0.f;
+                u32x4 wr[LPF];
+#pragma unroll
+                for (int j = 0; j < LPF; ++j) wr[j] = *(const u32x4 *)(wb + j * 1024);
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wr[s % LPF]), __builtin_bit_cast(bf16x8, xq[s]), a, 0, 0, 0);
+                    if (s + LPF < KS) wr[s % LPF] = *(const u32x4 *)(wb + (s + LPF) * 1024);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+                    if (32 * b + 16 * t < C) {
+                        bf16x8 q8;
+                        const f32x4 b0 = *(const f32x4 *)(bq + 32 * b + 16 * t), b1 = *(const f32x4 *)(bq + 32 * b + 16 * t + 4);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { q8[e] = (__bf16)(a[8 * t + e] + b0[e]); q8[4 + e] = (__bf16)(a[8 * t + 4 + e] + b1[e]); }
+                        qf[2 * b + t] = __builtin_bit_cast(u32x4, q8);
+                        asm volatile("" : "+v"(qf[2 * b + t]));
+                    }
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();          // nobody reads the weight buffers any more: the ring is the key loop's from here on
+    } else if constexpr (QPROJ) {
+        // (experiments build, DA_LAST_QPROJ_DIRECT=1: every wave loads the fragments itself, one contiguous KB per request, PF requests ahead of their product)
+        if (wave_on) {
+            constexpr int KS = 16, NB = (C + 31) / 32, NJ = NB * KS, PF = 6;
+            const unsigned char *xrow = (const unsigned char *)p.x + ((size_t)(node0 + min(q0 + i, n_g - 1)) * (size_t)p.ldx + 8 * half) * 2;
+            u32x4 xq[KS];
+#pragma unroll
+            for (int s = 0; s < KS; ++s) xq[s] = *(const u32x4 *)(xrow + s * 32);
+            const unsigned char *wl = (const unsigned char *)p.wqs + (size_t)h * (NJ * 1024) + lane * 16;
+            // the head's C bias words -> this wave's own 768 B behind the flags (launch_optt sizes the LDS): requested first, stored behind the
+            // other requests, read back -- by other lanes of the SAME wave, whose LDS operations complete in order -- at the end of every chain
+            float *bq = (float *)(smem + NST * MSTAGE + 64) + wid * 192;          // (every lane stores its three words: 192 slots, the last 48 unused)
+            float bv[(C + 63) / 64];
+#pragma unroll
+            for (int k = 0; k < (C + 63) / 64; ++k) bv[k] = p.bias_q[h * C + min(lane + 64 * k, C - 1)];
+            u32x4 wr[PF];
+#pragma unroll
+            for (int j = 0; j < PF; ++j) wr[j] = *(const u32x4 *)(wl + j * 1024);
+#pragma unroll
+            for (int k = 0; k < (C + 63) / 64; ++k) bq[lane + 64 * k] = bv[k];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            bq += 8 * half;
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                f32x16 a;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) a[r] = 0.f;
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const int j = b * KS + s;
+                    __builtin_amdgcn_sched_barrier(0);
+                    a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wr[j % PF]), __builtin_bit_cast(bf16x8, xq[s]), a, 0, 0, 0);
+                    if (j + PF < NJ) wr[j % PF] = *(const u32x4 *)(wl + (j + PF) * 1024);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+                    if (32 * b + 16 * t < C) {
+                        bf16x8 q8;
+                        const f32x4 b0 =*(const f32x4 *)(bq + 32 * b + 16 * t), b1 = *(const f32x4 *)(bq + 32 * b + 16 * t + 4);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { q8[e] = (__bf16)(a[8 * t + e] + b0[e]); q8[4 + e] = (__bf16)(a[8 * t + 4 + e] + b1[e]); }
+                        qf[2 * b + t] = __builtin_bit_cast(u32x4, q8);
+                        asm volatile("" : "+v"(qf[2 * b + t]));          // (packed HERE: sixteen sums kept in fp32 until their first use are what spilled)
+                    }
+            }
+        }
+    } else {
         const unsigned char *qrow = (const unsigned char *)p.Q + ((size_t)h * np + pad0 + min(q0, n_g - 1) / 32 * 32 + i) * CF::ROWB;
 #pragma unroll
         for (int ch = 0; ch < CF::NCH; ++ch) qf[ch] = *(const u32x4 *)(qrow + ch * 32 + half * 16);
@@ -856,7 +1004,8 @@ bool attn_opt_took_virtual_rows() { return t_virt_taken; }
 
 template <int C, bool FOLD, bool MASKED, int NST, int MINB, int BK = 64, int VAR = 0, int NWV = 4>
 static int launch_optt(AttnDenseParams p, hipStream_t st) {
-    const int lds = NST * (OptK<C, BK>::STAGE + (MASKED ? 1024 : 0)) + 64 + (MASKED ? 256 + 512 : 0);
+    const int lds = NST * (OptK<C, BK>::STAGE + (MASKED ? 1024 : 0)) + 64 + (MASKED ? 256 + 512 : 0) + ((VAR & 8192) ? NWV * 768 : 0) +
+                    (((VAR & 16384) && NST * OptK<C, BK>::STAGE + 64 < 3 * 16384) ? 3 * 16384 - (NST * OptK<C, BK>::STAGE + 64) : 0);      // (8192: the waves' bias words; 16384: three 16 KB weight buffers over the ring)
     static bool attr_done[16] = {};           // per device: the attribute belongs to the device's copy of the function
     int dev = 0;
     DA_CHECK_HIP(hipGetDevice(&dev));
@@ -1689,6 +1838,35 @@ int pack_w_qs(int heads, int kin, int hc, const void *wd, void *packed, hipStrea
     return 0;
 }
 
+// Fragment-major image of the folded last layer's Q weights for k_attn_optt<144, true, false, .., 8192> (Q in the prologue):
+// packed[((h * NB + b) * KS + s) * 64 + lane] = the 16 bytes W[C h + 32 b + pi(lane & 31)][16 s + 8 (lane >> 5) .. + 7], NB = ceil(C / 32) blocks per head,
+// pi as in k_pack_w_qs; rows of the last block behind the head's C channels are zeros.  W: the Q rows [heads * C][kin] (already carrying the softmax scale).
+__global__ void k_pack_w_qlast(int heads, int C, int kin, const bf16_t *__restrict__ W, u32x4 *__restrict__ out) {
+    const int KS = kin >> 4, NB = (C + 31) >> 5;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, total = (size_t)heads * NB * KS * 64;
+    if (idx >= total) return;
+    const int lane = (int)(idx & 63), s = (int)((idx >> 6) % KS), hb = (int)((idx >> 6) / KS), b = hb % NB, h = hb / NB;
+    const int a = lane & 31, ch = 32 * b + ((a & 0x13) | (((a >> 2) & 1) << 3) | (((a >> 3) & 1) << 2));
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (ch < C) v = *(const u32x4 *)(W + ((size_t)h * C + ch) * kin + 16 * s + 8 * (lane >> 5));
+    out[idx] = v;
+}
+size_t w_qlast_bytes(int heads, int C, int kin) { return (size_t)heads * ((C + 31) >> 5) * kin * 64; }
+int pack_w_qlast(int heads, int C, int kin, const void *wq, void *packed, hipStream_t st) {
+    const size_t total = w_qlast_bytes(heads, C, kin) / 16;
+    k_pack_w_qlast<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(heads, C, kin, (const bf16_t *)wq, (u32x4 *)packed);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+static long long g_last_qproj_launches = 0;      // [DA_DBG_LAST_QPROJ_LAUNCHES]: launches of the folded last layer that projected Q in their prologue
+long long attn_last_qproj_launches(int reset) {
+    return reset ? __atomic_exchange_n(&g_last_qproj_launches, 0ll, __ATOMIC_RELAXED) : __atomic_load_n(&g_last_qproj_launches, __ATOMIC_RELAXED);
+}
+// the shapes k_attn_optt<144, true, false, .., 8192> takes (whether a caller ASKS for it is the caller's switch: da_config.disable_folds bit 256)
+bool attn_last_qproj_shape_ok(int heads, int C, int kin) {
+    return heads == 8 && C == 144 && kin == 256 && DA_XENV("DA_OPT_LAST", 0) == 0;
+}
+
 template <int NWV, bool QUEUE, bool KPF, int XV = 0>
 static int launch_res(const AttnDenseParams &p, hipStream_t st) {
     int lds = ((p.max_nodes + 63) >> 6) * OptK<32, 64>::STAGE + 16 + 128 + 256;          // + the queue word + the landing words (XV & 16) + the mask table (XV & 32)
@@ -1818,6 +1996,16 @@ int launch_attn_opt(const AttnDenseParams &p, int C, hipStream_t st) {
     // (two ring stages at three workgroups per CU; measured at the end of round 4: three stages at two workgroups per CU 189 - 191 us
     // against 178 in the harness at 64 puzzles, 99 against 92 at 32, the sampling step 0.717 against 0.703 ms -- occupancy, not ring depth)
     if (C == 144 && fold) {
+        // DEFAULT where the caller sets p.x (da_config.disable_folds bit 256 clear): Q projected in this kernel's prologue, the launch in front of it wrote K | V' only
+        if (p.x) {
+            DA_REQUIRE(!masked && attn_last_qproj_shape_ok(p.H, C, p.kin) && p.wqs && p.bias_q && !p.x_fm && !p.out_fm,
+                       "k_attn_optt: Q in the prologue requested for a layer that does not take it");
+            __atomic_fetch_add(&g_last_qproj_launches, 1ll, __ATOMIC_RELAXED);
+#ifdef DA_EXPERIMENTS
+            if (DA_XENV("DA_LAST_QPROJ_DIRECT", 0)) return launch_optt<144, true, false, 2, 3, 64, 8192>(p, st);          // the weight fragments as direct loads
+#endif
+            return launch_optt<144, true, false, 2, 3, 64, 8192 + 16384>(p, st);
+        }
         if (masked) {
 #ifdef DA_EXPERIMENTS
             if (DA_XENV("DA_OPT_MASKED_VAR", 0) == 30) return launch_optt<144, true, true, 2, 3, 64, 256>(p, st);

@@ -17,7 +17,7 @@ namespace da {
 da_config &cfg();
 
 // disable_folds bits
-enum { DA_FOLD_MLP2 = 1, DA_FOLD_LAST = 2, DA_FOLD_QSCALE = 4, DA_FOLD_DDIM = 8, DA_FOLD_TAIL = 16, DA_FOLD_HYBRID_OVERLAP = 32, DA_FOLD_ATTN_PROJ = 64, DA_FOLD_X_FM = 128 };
+enum { DA_FOLD_MLP2 = 1, DA_FOLD_LAST = 2, DA_FOLD_QSCALE = 4, DA_FOLD_DDIM = 8, DA_FOLD_TAIL = 16, DA_FOLD_HYBRID_OVERLAP = 32, DA_FOLD_ATTN_PROJ = 64, DA_FOLD_X_FM = 128, DA_FOLD_LAST_QPROJ = 256 };
 
 #ifdef DA_EXPERIMENTS
 inline int xenv_read(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }

@@ -101,9 +101,9 @@ __device__ __forceinline__ void astat_epilogue(const GemmParams &p, const f32x4 
                 if (p.qkv && (p.debug & (which == 3 ? 64 : 32))) continue;
                 T *dst;
                 if (!p.qkv) dst = (T *)p.out + (size_t)m * p.ldo + col;
-                else if (which == 3) dst = (T *)p.S + (size_t)m * p.HC + (col - 3 * p.HC);
+                else if (which == 3) dst = (T *)p.S + (size_t)m * p.HC + (col + p.qcol0 - 3 * p.HC);
                 else {
-                    const int f = col - which * p.HC;
+                    const int f = col + p.qcol0 - which * p.HC;
                         if (which == 2 && p.Cv > 0) {
                             const int h = (int)__umulhi((unsigned)f, p.Cvmagic), c = f - h * p.Cv;
                             dst = (T *)p.Vt + ((size_t)h * p.n_pad + rs.q[mi][k]) * p.Cv + c;
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_astat(GemmParams p) {
     load_bias(0, bz);
     for (int ti = 0; ti < t_end - t_beg; ++ti) {
         const int col0 = colblock(t_beg + ti) * 128;
-        const int which = p.qkv ? col0 / p.HC : 0;
+        const int which = p.qkv ? (col0 + p.qcol0) / p.HC : 0;
         f32x4 acc[2][4];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm_astat_rs(GemmParams p) {
             const int ti = tb + u;
             if (ti >= ntile) break;
             const int col0 = colblock(t_beg + ti) * 128;
-            const int which = QKV ? col0 / p.HC : 0;
+            const int which = QKV ? (col0 + p.qcol0) / p.HC : 0;
             float bz[4][4];
             load_bias(ti, bz);
             f32x4 acc[2][4];

@@ -96,7 +96,8 @@ struct GemmParams {
     unsigned Cmagic;   // ceil(2^32 / C): f / C == __umulhi(f, Cmagic) for the f < 2^16 that occur here
     int Cv; unsigned Cvmagic;   // Cv > 0: the V block holds heads of Cv channels (folded value heads) and there is no skip block
     void *Q, *Kb, *Vt, *S;
-    int nct, nt;     // column tiles of this launch, column tiles per workgroup
+    int qcol0 = 0;     // QKV scatter: column of the Q | K | V | skip row this launch's column 0 is (QkvScatter::col0; W and bias arrive offset by as many rows)
+    int nct, nt;    // column tiles of this launch, column tiles per workgroup
     int xcd_groups;  // > 0: 1-D grid, XCD-aware (row tile, column group) mapping with this many column groups
     int ksplit, kchunk;   // ksplit > 1 (XCD-aware grid only): blockIdx.y = reduction split z over [z kchunk, (z + 1) kchunk); out = partial [ksplit][M][ldo]
     unsigned long long *prof;   // DA_GEMM_PROBE builds: per-workgroup cycle breakdown [total, wait, mma, epilogue]

@@ -103,9 +103,9 @@ __device__ __forceinline__ void mfma_epilogue(const GemmParams &p, const f32x4 (
             //  the Q | K | V scatter instance; opaque here, they are recomputed per tile: three integer operations)
             if constexpr (sizeof(T) == 4) asm volatile("" : "+v"(slot));
             if (!p.qkv) dst = (T *)p.out + (size_t)m * p.ldo + col;
-            else if (which == 3) dst = (T *)p.S + (size_t)m * p.HC + (col - 3 * p.HC);
+            else if (which == 3) dst = (T *)p.S + (size_t)m * p.HC + (col + p.qcol0 - 3 * p.HC);
             else {
-                const int f = col - which * p.HC;
+                const int f = col + p.qcol0 - which * p.HC;
                 if (which == 2 && p.Cv > 0) {
                     const int h = (int)__umulhi((unsigned)f, p.Cvmagic), c = f - h * p.Cv;
                     dst = (T *)p.Vt + ((size_t)h * p.n_pad + slot) * p.Cv + c;
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_mfma(GemmParams p) {
 
     for (int ti = 0; ti < t_end - t_beg; ++ti) {
         const int col0 = (t_beg + ti) * 128;
-        const int which = QKV ? col0 / p.HC : 0;
+        const int which = QKV ? (col0 + p.qcol0) / p.HC : 0;
         // bias of this lane's output features, fetched under the MFMAs (the epilogue wants them in
         // registers: dependent scalar loads there cost microseconds per tile)
         float bz[4][4];
@@ -274,8 +274,9 @@ int launch_gemm_mfma(int prec, int M, int K, int Nout, const void *A, int lda, c
     { const char *e = DA_XENV_LIVE("DA_GEMM_DEBUG"); p.debug = e ? atoi(e) : 0; }
     if (qs) {
         const int nexp = qs->blocks > 0 ? qs->blocks * qs->HC : (qs->Cv > 0 ? 2 * qs->HC + (qs->HC / qs->C) * qs->Cv : 4 * qs->HC);
-        if (qs->HC % 128 != 0 || (qs->C & 7) || (qs->Cv & 7) || Nout != nexp || Nout % 128 != 0 || act != DA_ACT_NONE || res) return -1;
-        p.qkv = 1; p.HC = qs->HC; p.C = qs->C; p.n_pad = qs->n_pad; p.row_map = qs->row_map;
+        if (qs->HC % 128 != 0 || (qs->C & 7) || (qs->Cv & 7) || qs->col0 < 0 || qs->col0 % 128 != 0 || Nout != nexp - qs->col0 || Nout % 128 != 0 ||
+            act != DA_ACT_NONE || res) return -1;
+        p.qkv = 1; p.qcol0 = qs->col0; p.HC = qs->HC; p.C = qs->C; p.n_pad = qs->n_pad; p.row_map = qs->row_map;
         p.Cv = qs->Cv;
         p.Cvmagic = qs->Cv > 0 ? (unsigned)((((unsigned long long)1 << 32) + (unsigned)qs->Cv - 1) / (unsigned)qs->Cv) : 0;
         p.Cmagic = (unsigned)((((unsigned long long)1 << 32) + (unsigned)qs->C - 1) / (unsigned)qs->C);

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(576) void k_gemm_wreg(GemmParams p, int tiles_per_w
         dbase = (bf16_t *)p.out + colc;
         rstride = (size_t)p.ldo;
     } else {
-        const int which = min(colc / p.HC, 3), f = colc - which * p.HC;
+        const int which = min((colc + p.qcol0) / p.HC, 3), f = colc + p.qcol0 - which * p.HC;
         if (which == 2 && p.Cv > 0) {
             const int h = f / p.Cv, c = f - h * p.Cv;
             dbase = (bf16_t *)p.Vt + (size_t)h * p.n_pad * p.Cv + c;
@@ -326,7 +326,7 @@ __global__ __launch_bounds__(320) void k_gemm_wreg2(GemmParams p, int tiles_per_
         dbase = (bf16_t *)p.out + colc;
         rstride = (size_t)p.ldo;
     } else {
-        const int which = min(colc / p.HC, 3), f = colc - which * p.HC;
+        const int which = min((colc + p.qcol0) / p.HC, 3), f = colc + p.qcol0 - which * p.HC;
         if (which == 2 && p.Cv > 0) {
             const int h = f / p.Cv, c = f - h * p.Cv;
             dbase = (bf16_t *)p.Vt + (size_t)h * p.n_pad * p.Cv + c;

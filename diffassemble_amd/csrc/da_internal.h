@@ -137,6 +137,9 @@ struct QkvScatter {            // where the fused projection scatters its four c
     int HC, C, n_pad;
     int Cv = 0;                // > 0: three blocks only (Q | K | V'), V' heads Cv wide (folded value heads), no skip
     int blocks = 0;            // > 0: only the first `blocks` column blocks exist (2: a K | V-only projection hands its blocks in through the Q and K slots)
+    int col0 = 0;              // > 0 (a multiple of 128): the launch starts at this column of the Q | K | V | skip row -- Nout is that much shorter, W and bias are
+                               // handed in offset by col0 rows, every column lands where the full launch puts it (HC: the K | V' projection of a folded last
+                               // layer whose attention kernel projects Q itself).  Every kernel launch_gemm_mfma can pick takes it.
     const int32_t *row_map;    // node -> padded row
     void *Q, *K, *Vt, *S;      // [H][n_pad][C] x 3 (Vt keeps its name; V is row-major since the tr_b16 rewrite), [M][H*C]
 };
@@ -159,6 +162,14 @@ bool attn_qsf_applicable(int prec, int heads, int C, int kin, int n_graphs, int 
 // asks ONCE, when it is created, like for every other fold (da_denoiser::attn_qsf: it packs the weight image then or never); da_conv_dense_ex, which
 // keeps nothing between calls, asks per call
 bool attn_qsf_enabled();
+// da_attn_dense.hip / da_attn_opt.hip: the un-masked folded last layer with Q projected in the attention kernel's prologue (k_attn_optt<144, true, false, ..,
+// 8192>; DenseLayout::x / wqs = pack_w_qlast image / bias = the Q bias): whether launch_attn_dense takes the form for this layer, and the switch
+// (da_config.disable_folds bit 256, DA_FOLD_LAST_QPROJ, clear; asked once per denoiser at creation, per call by da_conv_dense_ex)
+bool attn_last_qproj_applicable(int prec, int heads, int C, int kin, int n_pad, int q_prescaled);
+bool attn_last_qproj_enabled();
+size_t w_qlast_bytes(int heads, int C, int kin);
+int pack_w_qlast(int heads, int C, int kin, const void *wq, void *packed, hipStream_t st);
+long long attn_last_qproj_launches(int reset);   // da_attn_opt.hip: launches of the folded last layer that projected Q themselves
 size_t w_qs_bytes(int heads, int kin);
 int pack_w_qs(int heads, int kin, int hc, const void *wd, void *packed, hipStream_t st);
 // wpacked: optional fragment-major copy of W (pack_w_xpanel) for the row-panel kernel (da_gemm_xpanel.hip)

@@ -164,6 +164,7 @@ class DenoiserEngine:
             _lib.check(self.lib.da_denoiser_create(C.byref(w), self.prec, _lib.stream_ptr(self.device),
                                                    C.byref(handle)))
         self.handle = handle
+        self._pid = os.getpid()            # a forked child must not destroy the parent's GPU objects (__del__)
         self.flags = int(self.lib.da_denoiser_flags(handle))
         self.dense_only = bool(self.flags & 4)     # complete graphs never need the CSR arrays (unless alpha is wanted)
         del keep                      # create() synchronised: the fp32 staging copies may go
@@ -176,7 +177,7 @@ class DenoiserEngine:
 
     def __del__(self):
         h = getattr(self, "handle", None)
-        if h is not None and h.value:
+        if h is not None and h.value and getattr(self, "_pid", None) == os.getpid():
             try:
                 self.lib.da_denoiser_destroy(h)
             except Exception:  # noqa: BLE001
@@ -961,24 +962,24 @@ def conv_dense_ex(plan: GraphPlan, x, weight, bias, heads, C_head, residual=None
 
 def debug_counters(reset=True):
     """da_debug_counters as a dict (fallback events of the shift-free softmax kernels since the last reset)."""
-    buf = (C.c_int64 * 8)()
-    _lib.check(_lib.lib().da_debug_counters(buf, 8, 1 if reset else 0))
+    buf = (C.c_int64 * 16)()
+    _lib.check(_lib.lib().da_debug_counters(buf, 16, 1 if reset else 0))
     return {name: int(buf[k]) for k, name in enumerate(_lib.DBG_COUNTERS)}
 
 
 def launch_counters(reset=True):
     """Which kernels took the layers since the last reset (da_debug_counters [DA_DBG_RES_LAUNCHES], [DA_DBG_VIRT_IN_LAUNCH]): launches of the
     K / V-resident hidden-layer kernel, masked hidden-layer launches that carried the exophormer's virtual rows.  NOTE: resets every counter."""
-    buf = (C.c_int64 * 8)()
-    _lib.check(_lib.lib().da_debug_counters(buf, 8, 1 if reset else 0))
+    buf = (C.c_int64 * 16)()
+    _lib.check(_lib.lib().da_debug_counters(buf, 16, 1 if reset else 0))
     return {name: int(buf[k]) for name, k in _lib.DBG_LAUNCH_COUNTERS.items()}
 
 
 def resident_attention_launches(reset=True):
     """Launches of the K / V-resident hidden-layer attention kernel (k_attn_res, da_attn_opt.hip) since the last reset
     (da_debug_counters [DA_DBG_RES_LAUNCHES]): lets a test assert which kernel took a layer.  NOTE: resets every counter."""
-    buf = (C.c_int64 * 8)()
-    _lib.check(_lib.lib().da_debug_counters(buf, 8, 1 if reset else 0))
+    buf = (C.c_int64 * 16)()
+    _lib.check(_lib.lib().da_debug_counters(buf, 16, 1 if reset else 0))
     return int(buf[4])
 
 

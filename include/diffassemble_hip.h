@@ -65,7 +65,10 @@ typedef struct da_config {
                                  /* the prologue of its K/V-resident attention kernel (no projection kernel),        */
                                  /* 128 such layers handing their rows to the next one in MFMA operand order         */
                                  /* (fragment-major over the padded slots; needs bit 64 clear; fixed per denoiser    */
-                                 /* at creation, like bit 64)                                                        */
+                                 /* at creation, like bit 64), 256 the folded last layer's Q projected in the        */
+                                 /* prologue of its attention kernel on complete graphs (bf16, conv input 256): the  */
+                                 /* projection kernel writes K | V' only, Q never exists in memory (fixed per        */
+                                 /* denoiser at creation; da_conv_dense_ex asks per call)                            */
     int32_t attn_level;          /* DA_ATTN_LEVEL: 0 = the general dense kernel only, 1 = + the optimistic ring      */
                                  /* kernels, 2 = + the K/V-resident hidden-layer kernel (default)                    */
     int32_t xpanel;              /* DA_ENABLE_XPANEL: -1 = row-panel projections for large Batches (largest graph    */
@@ -517,7 +520,8 @@ int da_attn_csr(int prec, const da_graph *g, int heads, int C, const void *qkvs,
 
 /* The same layer through the dense block-diagonal MFMA path (g->dense != 0): fused projection
  * qkvs = x[n_nodes, Din] @ w[4*H*C, Din]^T + b scattered into head-major Q / K / V, then the
- * flash-style attention kernel.  scratch: caller memory of da_attn_dense_scratch_bytes(),
+ * flash-style attention kernel.  scratch: caller memory of da_attn_dense_scratch_bytes()
+ * (regions Q | K | V | skip, and for C = 144 room for a weight image of da_conv_dense_ex behind them),
  * zero-filled once by the caller before first use.  Returns nonzero (and an error text) if the
  * shape is not supported by the dense kernels.                                              */
 size_t da_attn_dense_scratch_bytes(int prec, const da_graph *g, int heads, int C);
@@ -529,7 +533,10 @@ int da_conv_dense(int prec, const da_graph *g, int heads, int C, int Din, const 
  * exp2 of the raw scores, verified row sums, running-max fallback), and with the value heads FOLDED to 32 channels
  * (DA_CONV_FOLDED_V32, C = 144: w = Wq | Wk | V' [2*H*C + H*32, Din], no skip; out = [H][n_real][32] per-head normalised
  * sum_j softmax_j(q_i.k_j / sqrt(C)) v'_j in the act dtype -- the last conv of the 2D transformer arch composed with
- * final_mlp.0).  Also takes hybrid graphs (adjacency mask + remainder CSR of g).  No reference counterpart
+ * final_mlp.0).  With disable_folds bit 256 clear (read per call) the folded layer of a complete graph runs as the
+ * sampling loop runs it: the projection kernel writes the K | V' columns only, the attention kernel projects Q per 32-query slab
+ * in its prologue -- the scratch's Q region is neither written nor read, da_debug_counters [DA_DBG_LAST_QPROJ_LAUNCHES] counts
+ * the launch; bit-identical outputs.  Also takes hybrid graphs (adjacency mask + remainder CSR of g).  No reference counterpart
  * beyond da_conv_dense's (Transformer_GNN.py:32,38): kernel-level test entry for those paths.                          */
 #define DA_CONV_Q_PRESCALED 1
 #define DA_CONV_FOLDED_V32 2
@@ -559,7 +566,11 @@ enum {
                                            /* their own prologue (disable_folds bit 64 clear): no projection kernel   */
     DA_DBG_RES_FM_LAUNCHES = 7,            /* ... and of those, the launches that read their input rows fragment-major */
                                            /* (disable_folds bit 128 clear; DA_CONV_X_FM)                             */
-    DA_DBG_NCOUNTERS = 8
+    DA_DBG_LAST_QPROJ_LAUNCHES = 8,        /* launches of the folded last layer's attention kernel that projected Q   */
+                                           /* in their own prologue (disable_folds bit 256 clear): the projection     */
+                                           /* kernel in front wrote the K | V' columns only.  Added behind the first  */
+                                           /* eight: da_debug_counters fills as many as the caller has room for (>= 8) */
+    DA_DBG_NCOUNTERS = 9
 };
 int da_debug_counters(int64_t *out /* host [n] */, int n, int reset);
 
