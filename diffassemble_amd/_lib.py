@@ -141,6 +141,26 @@ class DaPcdTrainGrads(C.Structure):
     ]
 
 
+PN_LAYERS = 5             # conv1 / bn1 .. conv5 / bn5 of the PointNet encoder
+
+
+class DaPointnetWeights(C.Structure):
+    _fields_ = [("feat_dim", C.c_int32), ("reserved0", C.c_int32), ("w", _fp * PN_LAYERS), ("b", _fp * PN_LAYERS)]
+
+
+class DaPointnetTrainWeights(C.Structure):
+    _fields_ = [
+        ("feat_dim", C.c_int32), ("reserved0", C.c_int32),
+        ("w", _fp * PN_LAYERS), ("wt", _fp * PN_LAYERS), ("gamma", _fp * PN_LAYERS), ("beta", _fp * PN_LAYERS),
+        ("running_mean", _fp * PN_LAYERS), ("running_var", _fp * PN_LAYERS),
+        ("momentum", C.c_float * PN_LAYERS), ("eps", C.c_float * PN_LAYERS),
+    ]
+
+
+class DaPointnetTrainGrads(C.Structure):
+    _fields_ = [("w", _fp * PN_LAYERS), ("gamma", _fp * PN_LAYERS), ("beta", _fp * PN_LAYERS)]
+
+
 # passes of da_pcd_train_pass (include/diffassemble_hip.h, "Passes of the 3D encoder's training path"), enum order
 PCD_PASSES = ("PREMAP", "EDGE_STAT_A", "EDGE_STAT_B", "EDGE_BWD1", "EDGE_BWD2", "EDGE_BWD3", "C6_STAT", "C6_BWD1", "C6_BWD2", "C6_DX",
               "BN_FIN_FWD", "BN_FIN_BWD", "REV_ADJ", "GATHER", "PREMAP_WGRAD", "HEAD_BWD", "LIN0_GRAD", "VN_LIN", "VN_STAT", "VN_APPLY")
@@ -276,6 +296,14 @@ PROTOTYPES = {
     "da_pcd_train_backward": (C.c_int, [C.POINTER(DaPcdTrainWeights), C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp,
                                         C.POINTER(DaPcdTrainGrads), _fp, C.c_size_t, C.c_int, _fp]),
     "da_pcd_train_pass": (C.c_int, [C.c_int, C.POINTER(DaPcdPassArgs), _fp]),
+    "da_pointnet_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "da_pointnet_forward": (C.c_int, [C.POINTER(DaPointnetWeights), C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, C.c_size_t, _fp]),
+    "da_pointnet_train_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "da_pointnet_train_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "da_pointnet_train_forward": (C.c_int, [C.POINTER(DaPointnetTrainWeights), C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.c_size_t,
+                                            _fp, C.c_size_t, _fp]),
+    "da_pointnet_train_backward": (C.c_int, [C.POINTER(DaPointnetTrainWeights), C.c_int, C.c_int, _fp, _fp, C.c_int, _fp,
+                                             C.POINTER(DaPointnetTrainGrads), _fp, C.c_size_t, _fp]),
     "da_knn": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp]),
     "da_nearest_sq": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
     "da_metrics3d": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, C.c_float, _fp, _fp, _fp]),

@@ -26,11 +26,15 @@ class Eff_GAT_3d(DenoiserBase):
         self.use_vn_dgcnn_equiv_inv_mp = False
         # point-cloud encoders (efficient_gat_3d.py:73-97): once per sampling loop, not per step.  The
         # vector-neuron DGCNN the 3D configuration trains with (train_3d.py: backbone="vn_dgcnn") runs in the HIP library
-        # (da_pcd_encoder_forward, eval mode); the PointNet variants are not built: pass pcd_feats.
+        # (da_pcd_encoder_forward, eval mode), and so does the plain PointNet (da_pointnet_forward; its own default
+        # here); pointnet_inv / pointnet_plus / vnn are not built: pass pcd_feats.
         self.pcd_backbone = None
         if backbone in ("vn_dgcnn", "vn_dgcnn_inv"):
             from .vnn.vn_dgcnn import VN_DGCNN
             self.pcd_backbone = VN_DGCNN(feat_dim=128, inv=(backbone == "vn_dgcnn_inv"))
+        elif backbone == "pointnet":                   # efficient_gat_3d.py: PointNet(feat_dim=128)
+            from .pointnet import PointNet
+            self.pcd_backbone = PointNet(feat_dim=128)
         feat_dim = _FEAT_DIM[backbone]
         self.combined_features_dim = feat_dim + 32 + 32
         self.gnn_feat_dim = self.combined_features_dim
@@ -68,7 +72,8 @@ class Eff_GAT_3d(DenoiserBase):
         """efficient_gat_3d.py:230-236: pcd [P, N, 3] -> pcd_feats [P, feat_dim]."""
         if self.pcd_backbone is None:
             raise NotImplementedError(
-                "only the VN-DGCNN point-cloud encoders are built (backbone='vn_dgcnn' / 'vn_dgcnn_inv'): pass pcd_feats")
+                "the point-cloud encoders built are backbone='vn_dgcnn' / 'vn_dgcnn_inv' / 'pointnet'; 'pointnet_inv', "
+                "'pointnet_plus' and 'vnn' have none: pass pcd_feats")
         if self.freeze_backbone:
             # no gradient, but the backbone keeps its mode: in train() its BatchNorms still use and update batch statistics
             with torch.no_grad():

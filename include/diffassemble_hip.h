@@ -1147,6 +1147,66 @@ int da_colsum_f32(int M, int N, const float *A, int lda, float *out, void *scrat
 int da_enc_bank_grad(int n, const int32_t *table, const float *dbank, float *dW, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * PointNet fragment encoder (backbone="pointnet"; the reference's backbones/pointnet.py:8-43): five 1x1 convolutions
+ * 3 -> 64 -> 64 -> 64 -> 128 -> feat_dim without bias, a BatchNorm1d after each, ReLU after the first four, max over
+ * the points of a fragment.  fp32 throughout; the 64 / 128-wide layers run on v_mfma_f32_32x32x2_f32 with this wave's
+ * weight columns held in registers.  feat_dim: a multiple of 32, at most 128 (the training path: 128).
+ * Layer l = 0..4 is conv{l+1} / bn{l+1}; widths DA_PN_WIDTH = 3, 64, 64, 64, 128, feat_dim.
+ * ------------------------------------------------------------------------------------- */
+enum { DA_PN_LAYERS = 5 };
+typedef struct da_pointnet_weights {
+    int32_t feat_dim;
+    int32_t reserved0;
+    const float *w[DA_PN_LAYERS];            /* [cout][cin] row-major, eval BatchNorm's scale folded into the rows */
+    const float *b[DA_PN_LAYERS];            /* [cout]: the folded shift  beta - mean * gamma / sqrt(var + eps)   */
+} da_pointnet_weights;
+
+/* Scratch of da_pointnet_forward: the partial maxima of fragments that span several workgroups (may be 0). */
+size_t da_pointnet_workspace_bytes(int n_parts, int n_points, int feat_dim);
+
+/* eval(): points [n_parts, n_points, 3] fp32 -> out [n_parts, feat_dim], row stride ld_out floats.  n_parts >= 0,
+ * n_points >= 1.  ONE launch runs a 64-point tile through all five layers inside the CU and reduces the maximum over a
+ * workgroup's points; a fragment cut over several workgroups is finished by a small second pass over `workspace`
+ * (no floating-point atomics; the maxima start from -inf).  Stream-capturable. */
+int da_pointnet_forward(const da_pointnet_weights *w, int n_parts, int n_points, const float *points, float *out, int ld_out,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
+typedef struct da_pointnet_train_weights {
+    int32_t feat_dim;
+    int32_t reserved0;
+    const float *w[DA_PN_LAYERS];            /* conv weights [cout][cin]                                           */
+    const float *wt[DA_PN_LAYERS];           /* the same transposed, [cin][cout] (the backward's dX = dY W); wt[0] unused */
+    const float *gamma[DA_PN_LAYERS], *beta[DA_PN_LAYERS];
+    const float *running_mean[DA_PN_LAYERS], *running_var[DA_PN_LAYERS];
+    float momentum[DA_PN_LAYERS], eps[DA_PN_LAYERS];
+} da_pointnet_train_weights;
+
+/* Parameter gradients in the module's layouts; every output is ADDED to. */
+typedef struct da_pointnet_train_grads {
+    float *w[DA_PN_LAYERS], *gamma[DA_PN_LAYERS], *beta[DA_PN_LAYERS];
+} da_pointnet_train_grads;
+
+/* Saved state of one train forward: per layer mean / inverse standard deviation / scale / shift, the arg-max point of
+ * every (fragment, channel), and the pre-normalisation activations of all five layers (448 floats per point). */
+size_t da_pointnet_train_state_bytes(int n_parts, int n_points, int feat_dim);
+/* Scratch of the train forward and backward (the backward's two gradient maps, one activation map, split-GEMM partials). */
+size_t da_pointnet_train_workspace_bytes(int n_parts, int n_points, int feat_dim);
+
+/* train(): BatchNorm on the statistics of this call's M = n_parts * n_points >= 2 points (mean and biased variance;
+ * per-workgroup Welford partials in fp32, combined in one fixed order), out as da_pointnet_forward.  run_out [5][2][128]:
+ * the updated running mean (row 2 l) and running variance (row 2 l + 1, from the unbiased batch variance) of layer l.
+ * Ties of the maximum go to the lowest point index.  Bitwise reproducible. */
+int da_pointnet_train_forward(const da_pointnet_train_weights *w, int n_parts, int n_points, const float *points, float *out,
+                              int ld_out, float *run_out, void *state, size_t state_bytes, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
+/* Backward of that call: grad_out [n_parts, ld_g] -> the gradients of the five conv weights and (gamma, beta) pairs (added
+ * to `g`).  The points get no gradient.  Every row reduction runs in a fixed order: bitwise reproducible. */
+int da_pointnet_train_backward(const da_pointnet_train_weights *w, int n_parts, int n_points, const float *points,
+                               const float *grad_out, int ld_g, const void *state, const da_pointnet_train_grads *g,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Exphander graphs (dataset/puzzle_dataset.py:115-152 generate_random_regular_graph): the adjacency
  * bit rows of da_graph.mask for n_graphs graphs of n nodes and degree d, from the permutations the generator draws
  * (perms int64 [n_graphs, n]): bit j of row i of graph g = edge j -> i, rows of row_bytes bytes, graph g at

@@ -1,5 +1,5 @@
 """Milliseconds per training step of the 3D model at the reference's shape (train_3d.py: 32 shapes, max_num_part = 20, 1000
-points per fragment, START_X, vn_dgcnn, loss_type="all"), in the exact-fp32 and the bf16-operand mode, split into noising,
+points per fragment, START_X, loss_type="all"; --backbone vn_dgcnn (the default, D = 832) or pointnet (D = 192)), in the exact-fp32 and the bf16-operand mode, split into noising,
 encoder forward, denoiser forward, loss, loss backward + denoiser backward, encoder backward and optimizer.
 
 Every shape holds 20 fragments (640 pieces).  The phases run as the step runs them (GNN_Diffusion.q_sample_se3 ->
@@ -8,7 +8,7 @@ device events on the one stream; the backward is cut at d_feats (the encoder's f
 into the encoder's own backward), so the two backward phases add up to what ``loss.backward()`` does in one piece.  `--warmup`
 whole steps first, then the mean over `--reps` steps and the spread (min .. max) of the step total.  Synthetic seeded weights /
 inputs (oracle/weights.py, tests/golden/train3d_cases.py).  One JSON line per (arch, precision).
-Run:  python tools/train3d_step_time.py [--arch transformer] [--reps 10] [--warmup 3] [--frozen]
+Run:  python tools/train3d_step_time.py [--arch transformer] [--backbone pointnet] [--reps 10] [--warmup 3] [--frozen]
 """
 import argparse
 import json
@@ -26,6 +26,14 @@ from oracle import weights as W  # noqa: E402
 import train3d_cases as T3  # noqa: E402
 
 PHASES = ("noising", "encoder_fwd", "denoiser_fwd", "loss", "loss_denoiser_bwd", "encoder_bwd", "optimizer")
+
+
+def make_state(arch, D, steps=600, seed=0):
+    """T3.make_state at the denoiser width of the chosen backbone (832 with vn_dgcnn, 192 with pointnet)."""
+    import gcn_cases as GC
+    if arch == "gcn":
+        return GC.make_gcn_state(steps, 7, None, D, T3.HIDDEN, "3d", seed)
+    return W.make_denoiser_state(steps, 7, None, D=D, hidden=T3.HIDDEN, variant="3d", arch=arch, virt_nodes=T3.VIRT, seed=seed)
 
 
 def one_step(m, opt, b, frozen, dev):
@@ -65,6 +73,7 @@ def main():
     ap.add_argument("--points", type=int, default=1000)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--backbone", default="vn_dgcnn", choices=("vn_dgcnn", "pointnet"))
     ap.add_argument("--frozen", action="store_true", help="freeze_backbone=True: no encoder backward, FusedAdafactor alone")
     args = ap.parse_args()
     from diffassemble_amd.model.spatial_diffusion_3d_test_double_diffusion import GNN_Diffusion, ModelMeanType
@@ -78,9 +87,9 @@ def main():
              valids=T3.valids_of([n] * G, n).to(dev), n_batch=G, t=torch.from_numpy(rng.integers(0, 600, size=G))[batch].to(dev))
     for arch in args.arch.split(","):
         for precision in ("fp32", "bf16"):
-            m = GNN_Diffusion(steps=600, sampling="DDIM", model_mean_type=ModelMeanType.START_X, backbone="vn_dgcnn", architecture=arch,
+            m = GNN_Diffusion(steps=600, sampling="DDIM", model_mean_type=ModelMeanType.START_X, backbone=args.backbone, architecture=arch,
                               max_num_part=n, loss_type="all", freeze_backbone=args.frozen)
-            m.model.load_state_dict(T3.make_state(arch, 600, 0), strict=False)
+            m.model.load_state_dict(make_state(arch, m.model.gnn_feat_dim), strict=False)
             m = m.to(dev).train()
             m.model.train_engine(dev).precision = precision
             opt = m.configure_optimizers()
@@ -91,7 +100,7 @@ def main():
             torch.cuda.synchronize(dev)
             ms = np.array([[ev[i].elapsed_time(ev[i + 1]) for i in range(len(PHASES))] for ev in runs])
             total = ms.sum(1)
-            print(json.dumps(dict(arch=arch, precision=precision, shapes=G, parts=n, points=args.points, pieces=P, frozen_encoder=args.frozen,
+            print(json.dumps(dict(arch=arch, backbone=args.backbone, precision=precision, shapes=G, parts=n, points=args.points, pieces=P, frozen_encoder=args.frozen,
                                   optimizer=type(opt).__name__, **{f"{k}_ms": round(float(v), 3) for k, v in zip(PHASES, ms.mean(0))},
                                   step_ms=round(float(total.mean()), 3), step_ms_min=round(float(total.min()), 3),
                                   step_ms_max=round(float(total.max()), 3), reps=args.reps, warmup=args.warmup)), flush=True)
