@@ -439,7 +439,9 @@ class GNN_Diffusion(LightningModule):
     def _eval_step(self, batch, batch_idx):
         """validation_step / test_step, spatial_diffusion.py:775-903,915-: sampling loop, greedy
         assignment of predicted positions to the grid, puzzle / piece accuracy.  The whole Batch is scored by one
-        ``score2d.batch_scores`` call (da_score2d); the metrics are updated from its one host copy."""
+        ``score2d.batch_scores`` call (da_score2d); the metrics are updated from its one host copy.  With
+        ``save_eval_images`` (:957-971) every step of the loop is then rendered for every puzzle (da_render2d) and
+        handed to ``save_eval_frame``; off, the default, nothing of that runs."""
         imgs, _ = self.p_sample_loop(batch.x.shape, batch.patches, batch.edge_index, batch=batch.batch,
                                      patch_feats=getattr(batch, "patch_feats", None), expander=self._expander_of(batch))
         img = imgs[-1]
@@ -458,7 +460,62 @@ class GNN_Diffusion(LightningModule):
                                   ("overall__piece_acc", piece_accuracy), ("overall_nImages", 1)):
                     if name in self.metrics:
                         self.metrics[name].update(val)
+        if self.save_eval_images:
+            self._save_eval_frames(batch, imgs)
         return img
+
+    # ------------------------------------------------------------------ pictures (spatial_diffusion.py:957-971, 1204-1234)
+    eval_image_dir = "results/test"       # where the default save_eval_frame writes
+    eval_image_max_bytes = 1 << 30        # frame buffer of one render_frames call of _eval_step
+
+    def create_image_from_patches(self, patches, pos, n_patches=(4, 4), i=0, rotations=None):
+        """spatial_diffusion.py:1204-1234 with the reference's signature: the pieces of ONE puzzle pasted where ``pos`` puts
+        them (and turned by ``rotations`` = (cos, sin) rows), as a ``PIL.Image`` in mode RGBA.  The frame is made by
+        ``render2d.batch_frames`` (one da_render2d launch on a ROCm device), bit-equal to the reference's PIL compositing."""
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise ImportError("create_image_from_patches returns a PIL.Image and PIL is not installed; "
+                              "diffassemble_amd.render2d.batch_frames gives the same pixels as a uint8 tensor without PIL") from e
+        from ..render2d import batch_frames
+        poses = pos[:, :2] if rotations is None else torch.cat((pos[:, :2], rotations[:, :2].to(pos.device)), 1)
+        frame = batch_frames(patches, poses.to(patches.device), [[int(n_patches[0]), int(n_patches[1])]], rotation=rotations is not None)[0][0]
+        return Image.fromarray(frame.cpu().numpy())
+
+    def render_frames(self, batch, imgs, steps=None, max_bytes=None):
+        """The pictures of a Batch along the sampling loop: ``frames[k][g]`` = uint8 [32 * rows_g, 32 * cols_g, 4] on the device
+        for the selected ``steps`` of ``imgs`` (the list ``p_sample_loop`` returns, or one [N, c] pose tensor) and every puzzle g
+        (``render2d.batch_frames``: one launch for all of them)."""
+        from ..render2d import MAX_BYTES, batch_frames
+        return batch_frames(batch.patches, imgs, batch.patches_dim, batch=batch.batch, rotation=bool(self.rotation), steps=steps,
+                            max_bytes=MAX_BYTES if max_bytes is None else max_bytes)
+
+    def save_eval_frame(self, frame, ind_name, step):
+        """Receives every frame ``_eval_step`` renders when ``save_eval_images`` is set: ``frame`` uint8 [H, W, 4] on the device,
+        ``ind_name`` the puzzle's ``ind_name`` in the Batch (its index in the Batch when the dataset attached none), ``step`` the
+        index of the loop step.  Default: ``<eval_image_dir>/{ind_name:03d}_{step:03d}.png`` through PIL.  Override or assign
+        another callable to keep the frames elsewhere."""
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise ImportError("save_eval_images writes PNG files through PIL, which is not installed; "
+                              "assign save_eval_frame to take the frames of render2d.batch_frames without PIL") from e
+        os.makedirs(self.eval_image_dir, exist_ok=True)
+        Image.fromarray(frame.cpu().numpy()).save(os.path.join(self.eval_image_dir, f"{int(ind_name):03d}_{int(step):03d}.png"))
+
+    def _save_eval_frames(self, batch, imgs):
+        """Every step of the loop for every puzzle, rendered in chunks of steps whose frames fit ``eval_image_max_bytes``."""
+        dims = torch.as_tensor(batch.patches_dim).reshape(-1, 2).tolist()
+        names = getattr(batch, "ind_name", None)
+        names = list(range(len(dims))) if names is None else [int(v) for v in torch.as_tensor(names).reshape(-1).tolist()]
+        per_step = sum(4 * 32 * r * 32 * c for r, c in dims)
+        chunk = max(1, int(self.eval_image_max_bytes) // per_step)
+        for lo in range(0, len(imgs), chunk):
+            picked = list(range(lo, min(lo + chunk, len(imgs))))
+            frames = self.render_frames(batch, imgs, steps=picked, max_bytes=max(int(self.eval_image_max_bytes), per_step))
+            for k, step in enumerate(picked):
+                for g, frame in enumerate(frames[k]):
+                    self.save_eval_frame(frame, names[g], step)
 
     def validation_step(self, batch, batch_idx):
         return self._eval_step(batch, batch_idx)

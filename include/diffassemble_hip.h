@@ -839,6 +839,29 @@ int da_score2d(int n_puzzles, const float *pred, int ld_pred, const float *gt, i
                int32_t *cell_pred, int32_t *cell_gt, uint8_t *piece_ok, int32_t *per_puzzle, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The assembled puzzles of a 2D Batch as RGBA pictures: every requested (step, puzzle) frame in ONE launch, one workgroup
+ * per 32x32 canvas tile, no atomics, no host sync, no allocation (it borrows every buffer).  Replaces the per-piece PIL
+ * compositing of create_image_from_patches (spatial_diffusion.py:1204-1234), which test_step and predict_step call once per
+ * loop step and puzzle when save_eval_images is set (:957-971, :1170-1202).
+ * Per puzzle g, `puzzles` [n_puzzles, 8] int32 holds: first piece, pieces, rows, cols, the fp32 bits of the x scale
+ * (float)(1 - 1 / rows) and of the y scale (float)(1 - 1 / cols) -- rows scales x: the reference's pairing --, and the low
+ * and high word of the frame's byte offset inside one step (a multiple of 16).  The canvas is [32 * rows, 32 * cols, 4]
+ * uint8, zeros where no piece lies.  Piece p (row p of `patches` [n_pieces, 3, 32, 32] fp32, colour = uint8(trunc(v * 255)),
+ * alpha 255) is padded by 7 transparent pixels to 46x46, rotated, and pasted with its alpha as the mask at
+ * x_pos = int((pos0 * xscale + 1) * W / 2) - 23, y_pos likewise with pos1, yscale and H (fp32, this order, no FMA, int()
+ * truncating toward zero); later pieces lie over earlier ones; everything is clipped.  A piece with a non-finite position is
+ * not drawn (the reference raises there).  `poses`: row p of step k starts at poses + k * step_stride + p * ld_pose floats.
+ * `coef` [n_steps, n_pieces, 6] int32, or NULL for no rotation: the 16.16 fixed-point inverse map of PIL's nearest-neighbour
+ * Image.rotate about (23, 23), a0 .. a5 with source x = (a2 + a0 * dx + a1 * dy) >> 16, source y = (a5 + a3 * dx + a4 * dy)
+ * >> 16 for the pixel (dx, dy) of the rotated tile; made on the host (fp64 cos / sin rounded to 15 decimals).
+ * `out`: step k's frames start at out + k * step_bytes.  max_tiles = max over the puzzles of rows * cols.
+ * da_render2d_frame_bytes: the bytes of one rows x cols frame (0 for a non-positive size).
+ * ------------------------------------------------------------------------------------- */
+long long da_render2d_frame_bytes(int rows, int cols);
+int da_render2d(int n_steps, int n_puzzles, int n_pieces, int max_tiles, const float *patches, const float *poses, int ld_pose,
+                long long step_stride, const int32_t *coef, const int32_t *puzzles, long long step_bytes, uint8_t *out, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * 2D piece encoder: the P4 group-equivariant ResNet-18 the reference builds
  * for model='resnet18equiv', eval-mode BatchNorm.  Replaces Eff_GAT.visual_features
  * (backbones/efficient_gat.py:149-189) = normalise + ResNet.forward (backbones/resnet_equivariant.py:
