@@ -276,19 +276,6 @@ static int check_graph(const da_denoiser *d, const da_graph *g) {
     return 0;
 }
 
-static DeviceSchedule to_dev(const da_schedule *s) {
-    DeviceSchedule r;
-    r.steps = s->steps;
-    r.betas = s->betas;
-    r.alphas_cumprod = s->alphas_cumprod;
-    r.sqrt_recip_alphas = s->sqrt_recip_alphas;
-    r.sqrt_recip_alphas_cumprod = s->sqrt_recip_alphas_cumprod;
-    r.sqrt_recipm1_alphas_cumprod = s->sqrt_recipm1_alphas_cumprod;
-    r.sqrt_one_minus_alphas_cumprod = s->sqrt_one_minus_alphas_cumprod;
-    r.posterior_variance = s->posterior_variance;
-    return r;
-}
-
 // Bracket one launch with a (start, stop) event pair on the launch stream when profiling.
 template <typename F>
 static int timed(da_denoiser *d, int cls, hipStream_t st, F &&launch) {

@@ -5,39 +5,13 @@
 // The reference keeps three [steps, K, K] fp32 tables and inverts a [N, K, K] batch per sampling step.  For the uniform kernel
 // Q_t = (1 - b_t) I + b_t / K 11^T every product of such matrices is again of that form: overline_Q[t] = a_t I + (1 - a_t) / K 11^T
 // with a_t = alphas_cumprod[t], and overline_Q[t] overline_Q[p]^-1 = r I + (1 - r) / K 11^T with r = a_t / a_p.  The step below
-// therefore needs two scalars per node and no K x K object.
-#include <float.h>
-
+// therefore needs two scalars per node and no K x K object.  The embedding lookup is the position + rotation model's
+// kernel without its addend rows (da_d3pm_rot.hip).
 #include "da_common.h"
+#include "da_d3pm_common.h"
 #include "da_internal.h"
 
 namespace da {
-
-// ------------------------------------------------------------------------------------------
-// comb_in[r, F:F+32] = pos_emb[idx[r]] ; comb_in[r, F+32:F+64] = time_emb[t[r]]   (efficient_gat_discrete.py:81-86)
-// A pure gather: one thread per written element, 64 consecutive threads per node.  Indices outside [0, K) and timesteps outside
-// [0, steps) are clamped (k_embed_pos_time clamps t the same way).
-template <typename T>
-__global__ __launch_bounds__(256) void k_embed_idx_time(int n, int K, int F, int D, const int32_t *__restrict__ idx,
-                                                        const int64_t *__restrict__ t, int64_t t_scalar, int steps,
-                                                        const float *__restrict__ time_emb, const float *__restrict__ pos_emb,
-                                                        T *__restrict__ comb_in) {
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (size_t)n * 64) return;
-    const size_t r = e >> 6;
-    const int c = (int)(e & 63);
-    float v;
-    if (c < 32) {
-        int k = idx[r];
-        k = k < 0 ? 0 : (k >= K ? K - 1 : k);
-        v = pos_emb[(size_t)k * 32 + c];
-    } else {
-        int64_t ti = t ? t[r] : t_scalar;
-        ti = ti < 0 ? 0 : (ti >= steps ? steps - 1 : ti);
-        v = time_emb[ti * 32 + (c - 32)];
-    }
-    stf(comb_in + r * D + F + c, v);
-}
 
 // ------------------------------------------------------------------------------------------
 // (philox_uniform: da_internal.h, shared with the training-side noising of da_d3pm_train.hip)
@@ -54,9 +28,8 @@ __global__ __launch_bounds__(256) void k_d3pm_noise(const uint64_t *__restrict__
 //            attention outputs, D3pmRows): logits[j][k] into LDS, and to HBM only when asked.  Under guidance
 //            both passes' rows are multiplied and combined as (1 + w) cond - w uncond, each product rounded on its own, i.e. the
 //            values the two-forward eager path forms.  da_d3pm_step starts from given logits instead (logits_in).
-//   phase 2  one wave per node: max, sum of exponentials, then per k the posterior
-//               post[k] = log(f1[k] + 1e-8) + log(a_p pi[k] + (1 - a_p) / K + 1e-8),   f1[k] = r [k == x_t] + (1 - r) / K
-//            (log f1 takes two values per node), the Gumbel term and a first-index argmax.  t == 0: argmax of the logits.
+//   phase 2  one wave per node: d3pm_categorical (da_d3pm_common.h, the one copy both discrete models run) -- the posterior, the
+//            Gumbel term and a first-index argmax.  t == 0: argmax of the logits.
 // fp32 throughout; any K in [2, 1024]; no per-lane arrays (the K values live in LDS).
 constexpr int D3PM_ROWS = 8;
 
@@ -119,71 +92,19 @@ __global__ __launch_bounds__(256) void k_d3pm_tail(int n, int K, int H, D3pmRows
     __syncthreads();
     for (int j = wv; j < rows; j += 4) {
         const int r = row0 + j;
-        const float *l = lg + j * K;
-        int64_t ti = sp.t ? sp.t[r] : sp.t_scalar;
-        ti = ti < 0 ? 0 : (ti >= sp.s.steps ? sp.s.steps - 1 : ti);
-        const bool t0 = ti == 0;
-        float lf_hit = 0.f, lf_miss = 0.f, ap = 1.f, c2 = 0.f, m = 0.f, inv_s = 0.f;
-        int xt = 0;
-        if (!t0) {
-            int64_t tp = ti - sp.ratio;
-            tp = tp < 0 ? 0 : tp;                                   // (precondition: t >= ratio wherever t > 0)
-            const float at = sp.s.alphas_cumprod[ti];
-            ap = sp.s.alphas_cumprod[tp];
-            const float rr = at / ap, miss = ((ap - at) / ap) / (float)K;        // (1 - r) / K without the cancellation of 1 - r
-            lf_hit = logf(rr + miss + 1e-8f);
-            lf_miss = logf(miss + 1e-8f);
-            c2 = (1.0f - ap) / (float)K;
-            xt = sp.x_t[r];
-            m = -FLT_MAX;
-            for (int k = lane; k < K; k += 64) m = fmaxf(m, l[k]);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-            float s = 0.f;
-            for (int k = lane; k < K; k += 64) s += expf(l[k] - m);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-            inv_s = 1.0f / s;
-        }
-        float best = -INFINITY;
-        int bi = 0x7fffffff;
-        for (int k = lane; k < K; k += 64) {
-            float v = l[k];
-            if (!t0) {
-                const float pi = expf(v - m) * inv_s;
-                v = (k == xt ? lf_hit : lf_miss) + logf(fmaf(ap, pi, c2) + 1e-8f);
-            }
-            if (sp.post) sp.post[(size_t)r * K + k] = v;
-            if (!t0) {
-                const size_t e = (size_t)r * K + k;
-                float u = sp.noise ? sp.noise[e] : philox_uniform(sp.seed[0], (uint64_t)e + sp.seed[1], (uint32_t)sp.iteration);
-                u = fminf(fmaxf(u, FLT_MIN), 1.0f);
-                // -log(-log u); the inner term is floored at 2^-25 so that u == 1 (one generated value in 2^24) stays finite
-                v += -logf(fmaxf(-logf(u), 2.98023223876953125e-8f));
-            }
-            if (v > best) { best = v; bi = k; }                    // ascending k per lane: the first maximum stays
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-        }
-        if (lane == 0) sp.x_prev[r] = bi == 0x7fffffff ? 0 : bi;
+        float at, ap;
+        const bool t0 = d3pm_step_alphas(sp.s, sp.t, sp.t_scalar, sp.ratio, r, at, ap);
+        const int xp = d3pm_categorical(lg + j * K, K, lane, (size_t)r * K, t0, at, ap, t0 ? 0 : sp.x_t[r], sp.noise, sp.seed,
+                                        (uint32_t)sp.iteration, D3PM_WORD_SAMPLING, sp.post);
+        if (lane == 0) sp.x_prev[r] = xp;
     }
 }
 
 // ------------------------------------------------------------------------------------------ launchers
 int launch_embed_idx_time(int prec, int n, int K, int F, int D, const int32_t *idx, const int64_t *t, int64_t t_scalar, int steps,
                           const float *time_emb, const float *pos_emb, void *comb_in, hipStream_t st) {
-    if (n <= 0) return 0;
-    const unsigned grid = (unsigned)(((size_t)n * 64 + 255) / 256);
-    if (prec == DA_PREC_BF16)
-        k_embed_idx_time<bf16_t><<<grid, 256, 0, st>>>(n, K, F, D, idx, t, t_scalar, steps, time_emb, pos_emb, (bf16_t *)comb_in);
-    else
-        k_embed_idx_time<float><<<grid, 256, 0, st>>>(n, K, F, D, idx, t, t_scalar, steps, time_emb, pos_emb, (float *)comb_in);
-    DA_LAUNCH_CHECK();
-    return 0;
+    return launch_embed_idx_time_rot(prec, n, K, F, D, 0, idx, nullptr, t, t_scalar, steps, time_emb, pos_emb, comb_in, nullptr, 0, nullptr,
+                                     st);
 }
 
 int launch_d3pm_tail(int prec, int n, int K, int H, const D3pmRows *rows_c, const D3pmRows *rows_u, float cfg_w, const float *w2,
@@ -219,9 +140,7 @@ int da_d3pm_step(const da_schedule *s, int n, int K, const int32_t *x_t, const f
                (long long)t_scalar, inference_ratio);
     DA_REQUIRE(noise || seed || (!t && t_scalar <= 0), "da_d3pm_step: needs the uniforms (noise) or a seed");
     D3pmStep sp;
-    sp.s.steps = s->steps; sp.s.betas = s->betas; sp.s.alphas_cumprod = s->alphas_cumprod; sp.s.sqrt_recip_alphas = s->sqrt_recip_alphas;
-    sp.s.sqrt_recip_alphas_cumprod = s->sqrt_recip_alphas_cumprod; sp.s.sqrt_recipm1_alphas_cumprod = s->sqrt_recipm1_alphas_cumprod;
-    sp.s.sqrt_one_minus_alphas_cumprod = s->sqrt_one_minus_alphas_cumprod; sp.s.posterior_variance = s->posterior_variance;
+    sp.s = to_dev(s);
     sp.x_t = x_t; sp.t = t; sp.t_scalar = t_scalar; sp.ratio = inference_ratio; sp.noise = noise; sp.seed = seed; sp.iteration = iteration;
     sp.x_prev = x_prev; sp.post = post;
     return launch_d3pm_tail(DA_PREC_F32, n, K, 0, nullptr, nullptr, 0.f, nullptr, nullptr, logits, nullptr, &sp, (hipStream_t)stream);

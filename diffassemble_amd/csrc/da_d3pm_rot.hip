@@ -1,22 +1,23 @@
 // Discrete position + rotation diffusion (spatial_diffusion_discrete_rot.py over backbones/efficient_gat_discrete_rotation.py): what
 // differs from the position model of da_d3pm.hip.
-//   * the embedding: the lookup of k_embed_idx_time plus the ADDEND-ROW SELECT.  The reference rotates every crop by its accumulated
-//     rotation rot_acc and re-encodes it each step (:353, :373); rot_acc takes four values, so the hoisted feature share of mlp.0 exists
-//     as four images per Batch (da_denoiser_set_features_rot) and a step only copies row rot_acc[piece] of them into the `pre` operand
-//     of the K = 64 mlp.0 product -- in the launch that gathers pos_mlp / time_emb anyway;
+//   * the embedding: the lookup (pos_emb[idx] | time_emb[t]; the position model's too, with proj4 == NULL) plus the ADDEND-ROW
+//     SELECT.  The reference rotates every crop by its accumulated rotation rot_acc and re-encodes it each step (:353, :373); rot_acc
+//     takes four values, so the hoisted feature share of mlp.0 exists as four images per Batch (da_denoiser_set_features_rot) and a
+//     step only copies row rot_acc[piece] of them into the `pre` operand of the K = 64 mlp.0 product -- in the launch that gathers
+//     pos_mlp / time_emb anyway;
 //   * the tail: two heads (K-wide and 4-wide) over the [n, 64] post-GELU rows of final_mlp.0 | final_mlp_rot.0, two categorical
-//     posteriors of the uniform transition (the closed form of da_d3pm.hip, with K and with 4), and the loop's state update.
-// k_d3pm_tail itself is not touched: the position model's bits stay what they were.
-#include <float.h>
-
+//     posteriors of the uniform transition (d3pm_categorical of da_d3pm_common.h, the copy k_d3pm_tail runs too, with K and with 4),
+//     and the loop's state update.
 #include "da_common.h"
+#include "da_d3pm_common.h"
 #include "da_internal.h"
 
 namespace da {
 
 // ------------------------------------------------------------------------------------------
-// 64 consecutive threads per node, as k_embed_idx_time: thread c writes comb_in[r, F + c] and copies elements c, c + 64, ... of the
-// selected projection row.  rot_acc is taken mod 4 (it is one by construction); idx / t are clamped.
+// comb_in[r, F:F+32] = pos_emb[idx[r]] ; comb_in[r, F+32:F+64] = time_emb[t[r]]   (efficient_gat_discrete.py:81-86)
+// 64 consecutive threads per node: thread c writes comb_in[r, F + c] and, with proj4, copies elements c, c + 64, ... of the selected
+// projection row.  rot_acc is taken mod 4 (it is one by construction); idx / t are clamped (k_embed_pos_time clamps t the same way).
 template <typename T>
 __global__ __launch_bounds__(256) void k_embed_idx_time_rot(int n, int K, int F, int D, int hidden, const int32_t *__restrict__ idx,
                                                             const int32_t *__restrict__ rot_acc, const int64_t *__restrict__ t,
@@ -28,69 +29,15 @@ __global__ __launch_bounds__(256) void k_embed_idx_time_rot(int n, int K, int F,
     const size_t r = e >> 6;
     const int c = (int)(e & 63);
     float v;
-    if (c < 32) {
-        int k = idx[r];
-        k = k < 0 ? 0 : (k >= K ? K - 1 : k);
-        v = pos_emb[(size_t)k * 32 + c];
-    } else {
-        int64_t ti = t ? t[r] : t_scalar;
-        ti = ti < 0 ? 0 : (ti >= steps ? steps - 1 : ti);
-        v = time_emb[ti * 32 + (c - 32)];
-    }
+    if (c < 32)
+        v = pos_emb[(size_t)clamp_idx(idx[r], K) * 32 + c];
+    else
+        v = time_emb[clamp_t(t ? t[r] : t_scalar, steps) * 32 + (c - 32)];
     stf(comb_in + r * D + F + c, v);
+    if (!proj4) return;
     const int img = rot_acc ? (rot_acc[r] & 3) : 0;
     const T *src = proj4 + (size_t)img * img_stride + r * hidden;
     for (int q = c; q < hidden; q += 64) sel[r * hidden + q] = src[q];
-}
-
-// ------------------------------------------------------------------------------------------
-// One wave, one node, one categorical variable with Kc categories whose logits l[] lie in LDS: the posterior of k_d3pm_tail's phase 2
-// (same expressions, same order), the Gumbel term and a first-index argmax; every lane returns the winner.  t0: the argmax of the
-// logits.  e0 = r * Kc: the node's first flat element (noise index, generator counter); `word` names the draw domain.
-__device__ __forceinline__ int d3pm_categorical(const float *l, int Kc, int lane, size_t e0, bool t0, float at, float ap_, int xt,
-                                                const float *noise, const uint64_t *seed, uint32_t iteration, uint32_t word,
-                                                float *post) {
-    float lf_hit = 0.f, lf_miss = 0.f, ap = 1.f, c2 = 0.f, m = 0.f, inv_s = 0.f;
-    if (!t0) {
-        ap = ap_;
-        const float rr = at / ap, miss = ((ap - at) / ap) / (float)Kc;        // (1 - r) / K without the cancellation of 1 - r
-        lf_hit = logf(rr + miss + 1e-8f);
-        lf_miss = logf(miss + 1e-8f);
-        c2 = (1.0f - ap) / (float)Kc;
-        m = -FLT_MAX;
-        for (int k = lane; k < Kc; k += 64) m = fmaxf(m, l[k]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        float s = 0.f;
-        for (int k = lane; k < Kc; k += 64) s += expf(l[k] - m);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        inv_s = 1.0f / s;
-    }
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int k = lane; k < Kc; k += 64) {
-        float v = l[k];
-        if (!t0) {
-            const float pi = expf(v - m) * inv_s;
-            v = (k == xt ? lf_hit : lf_miss) + logf(fmaf(ap, pi, c2) + 1e-8f);
-        }
-        if (post) post[e0 + k] = v;
-        if (!t0) {
-            const size_t e = e0 + k;
-            float u = noise ? noise[e] : philox_uniform(seed[0], (uint64_t)e + seed[1], iteration, word);
-            u = fminf(fmaxf(u, FLT_MIN), 1.0f);
-            v += -logf(fmaxf(-logf(u), 2.98023223876953125e-8f));          // -log(-log u), floored as in k_d3pm_tail
-        }
-        if (v > best) { best = v; bi = k; }                                // ascending k per lane: the first maximum stays
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    return bi == 0x7fffffff ? 0 : bi;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -151,16 +98,8 @@ __global__ __launch_bounds__(256) void k_d3pm_rot_tail(int n, int K, const T *__
     __syncthreads();
     for (int j = wv; j < rows; j += 4) {
         const int r = row0 + j;
-        int64_t ti = sp.t ? sp.t[r] : sp.t_scalar;
-        ti = ti < 0 ? 0 : (ti >= sp.s.steps ? sp.s.steps - 1 : ti);
-        const bool t0 = ti == 0;
-        float at = 1.f, ap = 1.f;
-        if (!t0) {
-            int64_t tp = ti - sp.ratio;
-            tp = tp < 0 ? 0 : tp;                                   // (precondition: t >= ratio wherever t > 0)
-            at = sp.s.alphas_cumprod[ti];
-            ap = sp.s.alphas_cumprod[tp];
-        }
+        float at, ap;
+        const bool t0 = d3pm_step_alphas(sp.s, sp.t, sp.t_scalar, sp.ratio, r, at, ap);
         const int xp = d3pm_categorical(lg + j * K, K, lane, (size_t)r * K, t0, at, ap, t0 ? 0 : sp.x_t[r], sp.noise_x, sp.seed,
                                         (uint32_t)sp.iteration, D3PM_WORD_SAMPLING, sp.post_x);
         const float *q = rl + j * 4;
@@ -240,9 +179,7 @@ int da_d3pm_rot_step(const da_schedule *s, int n, int K, const int32_t *x_t, con
     const bool need_prev = rot_prev || post_rot;
     DA_REQUIRE((noise_x && (noise_rot || !need_prev)) || seed || (!t && t_scalar <= 0), "da_d3pm_rot_step: needs the uniforms (noise_x, noise_rot) or a seed");
     D3pmRotStep sp;
-    sp.s.steps = s->steps; sp.s.betas = s->betas; sp.s.alphas_cumprod = s->alphas_cumprod; sp.s.sqrt_recip_alphas = s->sqrt_recip_alphas;
-    sp.s.sqrt_recip_alphas_cumprod = s->sqrt_recip_alphas_cumprod; sp.s.sqrt_recipm1_alphas_cumprod = s->sqrt_recipm1_alphas_cumprod;
-    sp.s.sqrt_one_minus_alphas_cumprod = s->sqrt_one_minus_alphas_cumprod; sp.s.posterior_variance = s->posterior_variance;
+    sp.s = to_dev(s);
     sp.x_t = x_t; sp.rot_t = rot_t; sp.t = t; sp.t_scalar = t_scalar; sp.ratio = inference_ratio; sp.noise_x = noise_x; sp.noise_rot = noise_rot;
     sp.seed = seed; sp.iteration = iteration; sp.x_prev = x_prev; sp.rot_0 = rot_0; sp.rot_prev = rot_prev; sp.post_x = post_x; sp.post_rot = post_rot;
     sp.need_prev = need_prev ? 1 : 0;

@@ -10,6 +10,10 @@ struct DeviceSchedule {
     const float *betas, *alphas_cumprod, *sqrt_recip_alphas, *sqrt_recip_alphas_cumprod,
         *sqrt_recipm1_alphas_cumprod, *sqrt_one_minus_alphas_cumprod, *posterior_variance;
 };
+inline DeviceSchedule to_dev(const da_schedule *s) {
+    return {s->steps, s->betas, s->alphas_cumprod, s->sqrt_recip_alphas, s->sqrt_recip_alphas_cumprod, s->sqrt_recipm1_alphas_cumprod,
+            s->sqrt_one_minus_alphas_cumprod, s->posterior_variance};
+}
 
 // DDIM update of one element, p_sample_ddim spatial_diffusion.py:555-566,603-627 (fp32, op order kept); shared by
 // k_ddim2d and the fused tail of the folded head (k_head_fold), so both produce the same bits.
@@ -269,6 +273,7 @@ struct D3pmStep {
     int32_t *x_prev = nullptr;
     float *post = nullptr;               // nullable [n, K]: the posterior logits before the Gumbel term
 };
+// launch_embed_idx_time_rot (below) without the addend rows
 int launch_embed_idx_time(int prec, int n, int K, int F, int D, const int32_t *idx, const int64_t *t, int64_t t_scalar, int steps,
                           const float *time_emb, const float *pos_emb, void *comb_in, hipStream_t st);
 // where a pass left its final_mlp.0 rows: post-GELU `hh` [n, 32], or (last-layer fold) the per-head outputs `pz` [H, n, 32] of the folded
@@ -301,14 +306,19 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t ctr, uin
 }
 // da_d3pm_train.hip: pos_mlp.weight.grad[idx[r]] += dcomb[r, F : F + 32], one owner per table row, fixed order
 int launch_embed_idx_grad(int n, int K, int D, int F, const int32_t *idx, const float *dcomb, float *grad, hipStream_t st);
+// the training-side noising of both discrete models, either half optional: x_noisy NULL skips the K-wide position draw, rot_noisy NULL
+// the four-wide rotation draw
+int launch_d3pm_q_sample(int n, int K, const da_schedule *s, const int32_t *x_start, const int32_t *rot_start, const int64_t *t,
+                         const float *noise_x, const float *noise_rot, const uint64_t *seed, int iteration, int32_t *x_noisy,
+                         int32_t *rot_noisy, hipStream_t st);
 // logits from the conditional rows (and the unconditional ones under guidance) through w2 / b2, or given (logits_in: rows_c may be
 // NULL); logits_out nullable; step == NULL: logits only
 int launch_d3pm_tail(int prec, int n, int K, int H, const D3pmRows *rows_c, const D3pmRows *rows_u, float cfg_w, const float *w2,
                      const float *b2, const float *logits_in, float *logits_out, const D3pmStep *step, hipStream_t st);
 
-// da_d3pm_rot.hip: the position + rotation variant (DA_VARIANT_DISCRETE_ROT).  The embedding lookup of launch_embed_idx_time that also
-// copies row rot_acc[r] of the four hoisted feature projections proj4 [4][img_stride] (rows of `hidden` elements, act dtype) into
-// `sel` [n, hidden], the addend of the K = 64 mlp.0 product; rot_acc NULL = image 0
+// da_d3pm_rot.hip: the position + rotation variant (DA_VARIANT_DISCRETE_ROT).  The embedding lookup (pos_emb[idx] | time_emb[t] into
+// comb_in) that, given proj4, also copies row rot_acc[r] of the four hoisted feature projections proj4 [4][img_stride] (rows of `hidden`
+// elements, act dtype) into `sel` [n, hidden], the addend of the K = 64 mlp.0 product; rot_acc NULL = image 0
 int launch_embed_idx_time_rot(int prec, int n, int K, int F, int D, int hidden, const int32_t *idx, const int32_t *rot_acc, const int64_t *t,
                               int64_t t_scalar, int steps, const float *time_emb, const float *pos_emb, void *comb_in, const void *proj4,
                               size_t img_stride, void *sel, hipStream_t st);

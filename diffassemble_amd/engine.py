@@ -19,6 +19,24 @@ def _f32(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+def _i32(t, device):
+    return t.detach().to(device=device, dtype=torch.int32).contiguous()
+
+
+def _t_arg(t, device):
+    """A timestep as the C entries take it: (int64 [N] device tensor, 0) for a tensor, (None, value) for a python int."""
+    if torch.is_tensor(t):
+        return t.detach().to(device=device, dtype=torch.int64).contiguous(), 0
+    return None, int(t)
+
+
+def _rocm(name, device):
+    """The kernel-level helpers' guard: entry ``name`` runs on ROCm tensors only.  Returns the device."""
+    if device.type != "cuda":
+        raise _lib.DaError(f"{name} needs ROCm tensors (no CPU path in diffassemble_amd)")
+    return device
+
+
 class Schedule:
     """Device copies of the registered diffusion buffers (spatial_diffusion.py:282-321)."""
 
@@ -354,12 +372,10 @@ class DenoiserEngine:
 
     # ------------------------------------------------------------------ discrete (D3PM) variant
     def _tt(self, t):
-        if torch.is_tensor(t):
-            return t.to(device=self.device, dtype=torch.int64).contiguous(), 0
-        return None, int(t)
+        return _t_arg(t, self.device)
 
     def _i32(self, x):
-        return x.detach().to(device=self.device, dtype=torch.int32).contiguous()
+        return _i32(x, self.device)
 
     def forward_idx(self, plan, idx, t, feats=None, return_alpha=False):
         """Eff_GAT_Discrete.forward_with_feats: position indices [N] (any integer dtype) -> logits [N, K] fp32
@@ -672,11 +688,8 @@ def d3pm_q_sample(sched: Schedule, x_start, t, K, noise=None, seed=None, iterati
     """The discrete forward noising (da_d3pm_q_sample, spatial_diffusion_discrete.py:181-191 in closed form): x_start [N] indices,
     t [N] int64 on a ROCm device -> x_t [N] int64.  ``noise`` [N, K] uniforms (parity tests), or ``seed`` (int64 [2] device tensor)
     for the kernel's own draw in the training domain -- no [N, K] buffer is made."""
-    dev = x_start.device
-    if dev.type != "cuda":
-        raise _lib.DaError("d3pm_q_sample needs ROCm tensors (no CPU path in diffassemble_amd)")
-    x0 = x_start.detach().to(device=dev, dtype=torch.int32).contiguous()
-    tt = t.detach().to(device=dev, dtype=torch.int64).contiguous()
+    dev = _rocm("d3pm_q_sample", x_start.device)
+    x0, tt = _i32(x_start, dev), _t_arg(t, dev)[0]
     nz = None if noise is None else _f32(noise, dev)
     n = x0.shape[0]
     if tt.shape != (n,) or (nz is not None and nz.shape != (n, int(K))):
@@ -692,16 +705,12 @@ def d3pm_loss(sched: Schedule, logits, x_start, x_t, t, kind="vb", lambda_loss=0
     """The loss of the discrete p_losses and its gradient with respect to the logits in one call (da_d3pm_loss): logits [N, K] fp32,
     x_start / x_t [N] indices, t [N] int64 on a ROCm device; kind "vb" | "cross_entropy" | "hybrid" (lambda_loss * ce + vb).
     Returns (loss [3] = {total, vb, ce}, d_logits [N, K] for a unit upstream gradient, row_terms [N, 2] = per-piece {vb, ce})."""
-    dev = logits.device
-    if dev.type != "cuda":
-        raise _lib.DaError("d3pm_loss needs ROCm tensors (no CPU path in diffassemble_amd)")
+    dev = _rocm("d3pm_loss", logits.device)
     if kind not in _lib.D3PM_LOSS:
         raise _lib.DaError(f"d3pm_loss: kind {kind!r} is not one of {sorted(_lib.D3PM_LOSS)}")
     z = _f32(logits, dev)
     n, K = z.shape
-    x0 = x_start.detach().to(device=dev, dtype=torch.int32).contiguous()
-    xt = x_t.detach().to(device=dev, dtype=torch.int32).contiguous()
-    tt = t.detach().to(device=dev, dtype=torch.int64).contiguous()
+    x0, xt, tt = _i32(x_start, dev), _i32(x_t, dev), _t_arg(t, dev)[0]
     if not (x0.shape == xt.shape == tt.shape == (n,)):
         raise _lib.DaError(f"d3pm_loss: logits {tuple(z.shape)} against x_start {tuple(x0.shape)}, x_t {tuple(xt.shape)}, t {tuple(tt.shape)}")
     loss = torch.empty(3, dtype=torch.float32, device=dev)
@@ -718,14 +727,11 @@ def d3pm_q_sample_rot(sched: Schedule, x_start, rot_start, t, K, noise_x=None, n
     indices, t [N] int64 on a ROCm device -> (x_t [N] int64 or None, rot_t [N] int64).  ``noise_x`` [N, K] / ``noise_rot`` [N, 4]
     uniforms, or ``seed`` (int64 [2] device tensor) for the kernel's own draws (training / training_rot domains).
     ``want_x=False`` skips the position half (only_rotation): ``x_start`` may then be None."""
-    dev = rot_start.device
-    if dev.type != "cuda":
-        raise _lib.DaError("d3pm_q_sample_rot needs ROCm tensors (no CPU path in diffassemble_amd)")
-    i32 = lambda x: x.detach().to(device=dev, dtype=torch.int32).contiguous()      # noqa: E731
-    r0 = i32(rot_start)
+    dev = _rocm("d3pm_q_sample_rot", rot_start.device)
+    r0 = _i32(rot_start, dev)
     n = r0.shape[0]
-    x0 = i32(x_start) if want_x else None
-    tt = t.detach().to(device=dev, dtype=torch.int64).contiguous()
+    x0 = _i32(x_start, dev) if want_x else None
+    tt = _t_arg(t, dev)[0]
     nx = None if noise_x is None or not want_x else _f32(noise_x, dev)
     nr = None if noise_rot is None else _f32(noise_rot, dev)
     if tt.shape != (n,) or (x0 is not None and x0.shape != (n,)) or (nx is not None and nx.shape != (n, int(K))) or \
@@ -746,22 +752,18 @@ def d3pm_rot_loss(sched: Schedule, logits, rot_logits, x_start, x_t, rot_start, 
     None: only_rotation, the position half is skipped) and rot_logits [N, 4] fp32, the four index vectors and t [N] on a ROCm
     device.  Returns (loss [6] = {x_loss, rot_loss, x_vb, x_ce, rot_vb, rot_ce}, d_logits [N, K] or None, d_rot_logits [N, 4],
     row_terms [N, 4]); the gradients are for unit upstream gradients of x_loss / rot_loss.  ``d_logits``: a caller's buffer."""
-    dev = rot_logits.device
-    if dev.type != "cuda":
-        raise _lib.DaError("d3pm_rot_loss needs ROCm tensors (no CPU path in diffassemble_amd)")
+    dev = _rocm("d3pm_rot_loss", rot_logits.device)
     if kind not in _lib.D3PM_LOSS:
         raise _lib.DaError(f"d3pm_rot_loss: kind {kind!r} is not one of {sorted(_lib.D3PM_LOSS)}")
-    i32 = lambda x: x.detach().to(device=dev, dtype=torch.int32).contiguous()      # noqa: E731
     zr = _f32(rot_logits, dev)
     n = zr.shape[0]
-    r0, rt = i32(rot_start), i32(rot_t)
-    tt = t.detach().to(device=dev, dtype=torch.int64).contiguous()
+    r0, rt, tt = _i32(rot_start, dev), _i32(rot_t, dev), _t_arg(t, dev)[0]
     if zr.shape != (n, 4) or not (r0.shape == rt.shape == tt.shape == (n,)):
         raise _lib.DaError(f"d3pm_rot_loss: rot_logits {tuple(zr.shape)} against rot_start {tuple(r0.shape)}, rot_t {tuple(rt.shape)}, t {tuple(tt.shape)}")
     z = x0 = xt = None
     K = 2
     if logits is not None:
-        z, x0, xt = _f32(logits, dev), i32(x_start), i32(x_t)
+        z, x0, xt = _f32(logits, dev), _i32(x_start, dev), _i32(x_t, dev)
         K = z.shape[1]
         if z.shape[0] != n or not (x0.shape == xt.shape == (n,)):
             raise _lib.DaError(f"d3pm_rot_loss: logits {tuple(z.shape)} against x_start {tuple(x0.shape)}, x_t {tuple(xt.shape)}, n {n}")
@@ -782,18 +784,13 @@ def d3pm_step(sched: Schedule, x_t, logits, t, ratio, noise=None, seed=None, ite
     """p_sample_ddpm after the model call (da_d3pm_step, spatial_diffusion_discrete.py:282-320): x_t [N] indices, logits [N, K] fp32
     on a ROCm device -> x_{t - ratio} [N] int64 (and the posterior logits [N, K] before the Gumbel term with ``return_post``).
     ``noise`` [N, K] uniforms, or ``seed`` (int64 [2] device tensor) for the kernel's own draw; t: int64 [N] tensor or python int."""
-    dev = logits.device
-    if dev.type != "cuda":
-        raise _lib.DaError("d3pm_step needs ROCm tensors (no CPU path in diffassemble_amd)")
-    x_t, logits = x_t.detach().to(device=dev, dtype=torch.int32).contiguous(), _f32(logits, dev)
+    dev = _rocm("d3pm_step", logits.device)
+    x_t, logits = _i32(x_t, dev), _f32(logits, dev)
     n, K = logits.shape
     out = torch.empty(n, dtype=torch.int32, device=dev)
     post = torch.empty_like(logits) if return_post else None
     nz = None if noise is None else _f32(noise, dev)
-    if torch.is_tensor(t):
-        tt, ts = t.to(device=dev, dtype=torch.int64).contiguous(), 0
-    else:
-        tt, ts = None, int(t)
+    tt, ts = _t_arg(t, dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().da_d3pm_step(C.byref(sched.c), n, K, _lib.ptr(x_t), _lib.ptr(logits), _lib.ptr(tt), ts, int(ratio),
                                            _lib.ptr(nz), _lib.ptr(seed), int(iteration), _lib.ptr(out), _lib.ptr(post),
@@ -806,11 +803,8 @@ def d3pm_rot_step(sched: Schedule, x_t, rot_t, logits, rot_logits, t, ratio, noi
     """p_sample_ddpm of the position + rotation model after the model call (da_d3pm_rot_step, spatial_diffusion_discrete_rot.py:
     288-330): -> (x_prev, rot_0, rot_prev) int64 [N] (and the two posteriors [N, K], [N, 4] before the Gumbel terms with
     ``return_post``).  ``noise_x`` [N, K] / ``noise_rot`` [N, 4] uniforms, or ``seed`` (int64 [2] device tensor)."""
-    dev = logits.device
-    if dev.type != "cuda":
-        raise _lib.DaError("d3pm_rot_step needs ROCm tensors (no CPU path in diffassemble_amd)")
-    i32 = lambda x: x.detach().to(device=dev, dtype=torch.int32).contiguous()      # noqa: E731
-    x_t, rot_t, logits, rot_logits = i32(x_t), i32(rot_t), _f32(logits, dev), _f32(rot_logits, dev)
+    dev = _rocm("d3pm_rot_step", logits.device)
+    x_t, rot_t, logits, rot_logits = _i32(x_t, dev), _i32(rot_t, dev), _f32(logits, dev), _f32(rot_logits, dev)
     n, K = logits.shape
     if rot_logits.shape != (n, 4) or x_t.shape != (n,) or rot_t.shape != (n,):
         raise _lib.DaError(f"d3pm_rot_step: logits {tuple(logits.shape)}, rot_logits {tuple(rot_logits.shape)}, x_t {tuple(x_t.shape)}, rot_t {tuple(rot_t.shape)}")
@@ -819,10 +813,7 @@ def d3pm_rot_step(sched: Schedule, x_t, rot_t, logits, rot_logits, t, ratio, noi
     rpost = torch.empty_like(rot_logits) if return_post else None
     nx = None if noise_x is None else _f32(noise_x, dev)
     nr = None if noise_rot is None else _f32(noise_rot, dev)
-    if torch.is_tensor(t):
-        tt, ts = t.to(device=dev, dtype=torch.int64).contiguous(), 0
-    else:
-        tt, ts = None, int(t)
+    tt, ts = _t_arg(t, dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().da_d3pm_rot_step(C.byref(sched.c), n, K, _lib.ptr(x_t), _lib.ptr(rot_t), _lib.ptr(logits), _lib.ptr(rot_logits),
                                                _lib.ptr(tt), ts, int(ratio), _lib.ptr(nx), _lib.ptr(nr), _lib.ptr(seed), int(iteration),

@@ -42,10 +42,10 @@ _OFF_DEVICE = _NOT_BUILT + " off the device: it runs on ROCm tensors only (diffa
 _LOSS_TYPES = ("vb", "cross_entropy", "hybrid")
 
 
-def _require_device(*tensors):
+def _require_device(message, *tensors):
     """The training methods' guard: every argument must be a tensor on a ROCm device."""
     if not tensors or not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
-        raise NotImplementedError(_OFF_DEVICE)
+        raise NotImplementedError(message)
 
 
 class _D3pmLoss(torch.autograd.Function):
@@ -102,23 +102,36 @@ class GNN_Diffusion(sd.GNN_Diffusion):
         s.random_()
         return s
 
+    def _draw_t(self, batch):
+        """training_step's timesteps: one draw per puzzle, gathered to the pieces ([N] int64)."""
+        batch_size = batch.batch.max().item() + 1
+        t = torch.randint(0, self.steps, (batch_size,), device=self.device).long()
+        return torch.gather(t, 0, batch.batch)
+
+    def _cfg_mask(self, patch_feats, batch, cfg_rand=None):
+        """p_losses' classifier-free mask: the features of the puzzles whose uniform is <= ``classifier_free_prob`` are zeroed;
+        ``cfg_rand`` [G] given or drawn (not drawn at all with ``classifier_free_prob == 0``)."""
+        if cfg_rand is None and not self.classifier_free_prob > 0.0:
+            return patch_feats
+        if cfg_rand is None:
+            cfg_rand = torch.rand(int(batch.max()) + 1, device=batch.device)
+        keep = cfg_rand.to(batch.device)[batch] > self.classifier_free_prob
+        return keep[:, None] * patch_feats
+
     def training_step(self, batch=None, batch_idx=0):
         """spatial_diffusion_discrete.py:93-141 without the ``batch_idx == 0`` sampling-and-image dump."""
         if batch is None or not hasattr(batch, "batch"):
             raise NotImplementedError(_OFF_DEVICE)
-        _require_device(batch.batch, batch.indexes)
-        batch_size = batch.batch.max().item() + 1
-        t = torch.randint(0, self.steps, (batch_size,), device=self.device).long()
-        new_t = torch.gather(t, 0, batch.batch)
-        loss = self.p_losses(batch.indexes % self.K, new_t, loss_type=self.loss_type, cond=batch.patches, edge_index=batch.edge_index,
-                             batch=batch.batch, patch_feats=getattr(batch, "patch_feats", None))
+        _require_device(_OFF_DEVICE, batch.batch, batch.indexes)
+        loss = self.p_losses(batch.indexes % self.K, self._draw_t(batch), loss_type=self.loss_type, cond=batch.patches,
+                             edge_index=batch.edge_index, batch=batch.batch, patch_feats=getattr(batch, "patch_feats", None))
         self.log("loss", loss)
         return loss
 
     def q_sample(self, x_start=None, t=None, overline_Q=None, eps=1e-9, noise=None):
         """spatial_diffusion_discrete.py:181-191 in closed form (da_d3pm_q_sample): ``x_start`` [N] indices (or the reference's one-hot
         [N, K]), ``t`` [N] -> x_t [N] int64.  ``noise`` (extension): the [N, K] uniforms; default: drawn inside the kernel."""
-        _require_device(x_start, t)
+        _require_device(_OFF_DEVICE, x_start, t)
         if overline_Q is not None or eps != 1e-9:
             raise NotImplementedError("q_sample: explicit transition tables / another eps are not supported (closed form only)")
         if x_start.dim() == 2:
@@ -132,7 +145,7 @@ class GNN_Diffusion(sd.GNN_Diffusion):
         p(x_{t-1} | x_t)) / ln 2, the decoder NLL where t == 0; differentiable with respect to ``pred_x_start_logits``.
         ``model_logits`` is accepted for the reference's signature and not read: the kernel forms the model posterior from the
         predicted logits itself (q_posterior_logits at previous_t = t - 1)."""
-        _require_device(pred_x_start_logits, x_start, x_t, t)
+        _require_device(_OFF_DEVICE, pred_x_start_logits, x_start, x_t, t)
         if overline_Q is not None or (K is not None and K != self.K):
             raise NotImplementedError("vb_terms_bpd: explicit transition tables / another K are not supported (closed form only)")
         return _D3pmLoss.apply(pred_x_start_logits, self._schedule(), x_start, x_t, t, "vb", float(self.lambda_loss))[0]
@@ -143,18 +156,14 @@ class GNN_Diffusion(sd.GNN_Diffusion):
         the [N, K] uniforms of the noising for parity runs, default in-kernel draws; ``cfg_rand`` (extension): the [G] uniforms of
         the classifier-free mask; ``patch_feats`` (extension) bypasses the piece encoder.  The three parts {total, vb, ce} of the
         last call stay in ``self.last_loss_parts`` (a [3] device tensor)."""
-        _require_device(x_start, t)
+        _require_device(_OFF_DEVICE, x_start, t)
         if loss_type not in _LOSS_TYPES:
             raise Exception("Loss not implemented %s", loss_type)
-        _require_device(edge_index, batch)
+        _require_device(_OFF_DEVICE, edge_index, batch)
         x_noisy = self.q_sample(x_start, t, noise=noise)
         if patch_feats is None:
             patch_feats = self.visual_features(cond)
-        if cfg_rand is not None or self.classifier_free_prob > 0.0:
-            if cfg_rand is None:
-                cfg_rand = torch.rand(int(batch.max()) + 1, device=batch.device)
-            keep = cfg_rand.to(batch.device)[batch] > self.classifier_free_prob
-            patch_feats = keep[:, None] * patch_feats
+        patch_feats = self._cfg_mask(patch_feats, batch, cfg_rand)
         prediction = self.forward_with_feats(x_noisy, t, cond, edge_index, patch_feats=patch_feats, batch=batch)
         loss, parts = _D3pmLoss.apply(prediction, self._schedule(), x_start, x_noisy, t, loss_type, float(self.lambda_loss))
         self.last_loss_parts = parts
@@ -226,11 +235,16 @@ class GNN_Diffusion(sd.GNN_Diffusion):
         Per-graph "all correct" is reduced on the device; one host copy per Batch carries it with the per-piece flags and sizes."""
         pred = self.p_sample_loop(batch.indexes.shape, batch.patches, batch.edge_index, batch=batch.batch,
                                   patch_feats=getattr(batch, "patch_feats", None))[-1]
-        gt = batch.indexes.to(pred.device) % self.K
-        ok = pred == gt
-        dims = batch.patches_dim.to(pred.device).long().reshape(-1, 2)
+        self._score(batch, pred == batch.indexes.to(pred.device) % self.K)
+        return pred
+
+    def _score(self, batch, ok):
+        """``_eval_step``'s bookkeeping from the per-piece flags ``ok`` [N] (device): the per-graph "all correct" reduction, the
+        single host copy, and the metric updates."""
+        dev = ok.device
+        dims = batch.patches_dim.to(dev).long().reshape(-1, 2)
         G = dims.shape[0]
-        wrong = torch.zeros(G, dtype=torch.long, device=pred.device).index_add_(0, batch.batch.to(pred.device), (~ok).long())
+        wrong = torch.zeros(G, dtype=torch.long, device=dev).index_add_(0, batch.batch.to(dev), (~ok).long())
         host = torch.cat([wrong == 0, ok, dims.flatten()]).cpu()
         correct, piece_ok, dims = host[:G].bool(), host[G:G + ok.numel()].float(), host[G + ok.numel():].reshape(G, 2).tolist()
         if hasattr(self, "metrics"):
@@ -244,4 +258,3 @@ class GNN_Diffusion(sd.GNN_Diffusion):
                 upd("overall_nImages", 1)
                 upd(f"{key}_acc", int(correct[i]))
                 upd("overall_acc", int(correct[i]))
-        return pred

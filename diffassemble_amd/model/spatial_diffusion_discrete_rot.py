@@ -41,12 +41,6 @@ _NOT_BUILT = "discrete-rotation training is not built yet"
 _OFF_DEVICE = _NOT_BUILT + " off the device: it runs on ROCm tensors only (diffassemble_amd has no CPU path)"
 
 
-def _require_device(*tensors):
-    """The training methods' guard: every argument must be a tensor on a ROCm device."""
-    if not tensors or not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
-        raise NotImplementedError(_OFF_DEVICE)
-
-
 class _D3pmRotLoss(torch.autograd.Function):
     """Both heads' losses with their gradients with respect to both logits computed in the SAME call (da_d3pm_rot_loss), like
     ``spatial_diffusion_discrete._D3pmLoss``: backward scales ``d_logits`` by the upstream gradient of ``x_loss`` and ``d_rot_logits``
@@ -91,12 +85,9 @@ class GNN_Diffusion(sdd.GNN_Diffusion):
         ``p_losses`` and ``"loss"`` = their sum, returns the sum."""
         if batch is None or not hasattr(batch, "batch"):
             raise NotImplementedError(_OFF_DEVICE)
-        _require_device(batch.batch, batch.indexes, batch.rot_index)
-        batch_size = batch.batch.max().item() + 1
-        t = torch.randint(0, self.steps, (batch_size,), device=self.device).long()
-        new_t = torch.gather(t, 0, batch.batch)
-        losses = self.p_losses(batch.indexes % self.K, new_t, rot_start=batch.rot_index % self.rot_K, loss_type=self.loss_type,
-                               cond=batch.patches, edge_index=batch.edge_index, batch=batch.batch,
+        sdd._require_device(_OFF_DEVICE, batch.batch, batch.indexes, batch.rot_index)
+        losses = self.p_losses(batch.indexes % self.K, self._draw_t(batch), rot_start=batch.rot_index % self.rot_K,
+                               loss_type=self.loss_type, cond=batch.patches, edge_index=batch.edge_index, batch=batch.batch,
                                patch_feats=getattr(batch, "patch_feats", None))
         self.log_dict(losses)
         loss_tot = sum(l for l in losses.values())
@@ -107,7 +98,7 @@ class GNN_Diffusion(sdd.GNN_Diffusion):
         """The rotation process' q_sample (``q_sample(one_hot(rot_start, 4), t, overline_Q_rot)``, :181-183) in closed form:
         ``rot_start`` [N] in {0..3}, ``t`` [N] -> rot_t [N] int64.  ``noise`` (extension): the [N, 4] uniforms; default: drawn
         inside the kernel (training_rot domain)."""
-        _require_device(rot_start, t)
+        sdd._require_device(_OFF_DEVICE, rot_start, t)
         from ..engine import d3pm_q_sample_rot
         seed = None if noise is not None else self._train_seed_tensor(rot_start.device)
         return d3pm_q_sample_rot(self._schedule(), None, rot_start, t, self.K, noise_rot=noise, seed=seed, want_x=False)[1]
@@ -117,7 +108,7 @@ class GNN_Diffusion(sdd.GNN_Diffusion):
         ``K=self.rot_K`` the rotation process (da_d3pm_loss at K = 4; ``overline_Q`` is accepted there for the reference's signature
         and not read: the closed form serves both)."""
         if K is not None and K == self.rot_K and K != self.K:
-            _require_device(pred_x_start_logits, x_start, x_t, t)
+            sdd._require_device(_OFF_DEVICE, pred_x_start_logits, x_start, x_t, t)
             if pred_x_start_logits.shape[-1] != self.rot_K:
                 raise ValueError(f"vb_terms_bpd(K={K}): logits of shape {tuple(pred_x_start_logits.shape)}")
             return sdd._D3pmLoss.apply(pred_x_start_logits, self._schedule(), x_start, x_t, t, "vb", float(self.lambda_loss))[0]
@@ -130,10 +121,10 @@ class GNN_Diffusion(sdd.GNN_Diffusion):
         ``noise_rot`` [N, 4] uniforms of the two noisings (default in-kernel draws), ``cfg_rand`` [G] uniforms of the classifier-free
         mask, ``patch_feats`` [N, 1088] bypasses the piece encoder.  ``self.last_loss_parts``: the [6] device tensor {x_loss,
         rot_loss, x_vb, x_ce, rot_vb, rot_ce} of the last call; ``self.last_noisy``: its (x_noisy, rot_noisy)."""
-        _require_device(x_start, t, rot_start)
+        sdd._require_device(_OFF_DEVICE, x_start, t, rot_start)
         if loss_type not in sdd._LOSS_TYPES:
             raise Exception("Loss not implemented %s", loss_type)
-        _require_device(edge_index, batch)
+        sdd._require_device(_OFF_DEVICE, edge_index, batch)
         from ..engine import d3pm_q_sample_rot
         only_rot = bool(self.only_rotation)
         need_seed = noise_rot is None or (noise is None and not only_rot)
@@ -145,11 +136,7 @@ class GNN_Diffusion(sdd.GNN_Diffusion):
         self.last_noisy = (x_noisy, rot_noisy)
         if patch_feats is None:
             patch_feats = self.visual_features(cond)
-        if cfg_rand is not None or self.classifier_free_prob > 0.0:
-            if cfg_rand is None:
-                cfg_rand = torch.rand(int(batch.max()) + 1, device=batch.device)
-            keep = cfg_rand.to(batch.device)[batch] > self.classifier_free_prob
-            patch_feats = keep[:, None] * patch_feats
+        patch_feats = self._cfg_mask(patch_feats, batch, cfg_rand)
         x_pred, rot_pred = self.forward_with_feats(x_noisy, t, cond, edge_index, patch_feats, rot_noisy, batch)
         x_loss, rot_loss, parts = _D3pmRotLoss.apply(None if only_rot else x_pred, rot_pred, self._schedule(), x_start, x_noisy,
                                                      rot_start, rot_noisy, t, loss_type, float(self.lambda_loss))
@@ -224,20 +211,5 @@ class GNN_Diffusion(sdd.GNN_Diffusion):
         dev = pred.device
         ok_rot = (pred_rot % self.rot_K) == (batch.rot_index.to(dev) % self.rot_K)
         ok = ok_rot if self.only_rotation else (pred == batch.indexes.to(dev) % self.K) & ok_rot
-        dims = batch.patches_dim.to(dev).long().reshape(-1, 2)
-        G = dims.shape[0]
-        wrong = torch.zeros(G, dtype=torch.long, device=dev).index_add_(0, batch.batch.to(dev), (~ok).long())
-        host = torch.cat([wrong == 0, ok, dims.flatten()]).cpu()
-        correct, piece_ok, dims = host[:G].bool(), host[G:G + ok.numel()].float(), host[G + ok.numel():].reshape(G, 2).tolist()
-        if hasattr(self, "metrics"):
-            def upd(name, val):
-                if name in self.metrics:
-                    self.metrics[name].update(val)
-            upd("overall__piece_acc", piece_ok)
-            for i in range(G):
-                key = f"{tuple(dims[i])}"
-                upd(f"{key}_nImages", 1)
-                upd("overall_nImages", 1)
-                upd(f"{key}_acc", int(correct[i]))
-                upd("overall_acc", int(correct[i]))
+        self._score(batch, ok)
         return pred, pred_rot

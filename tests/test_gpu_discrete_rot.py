@@ -91,6 +91,24 @@ def test_step_kernel(K, dev):
     assert all(torch.equal(p, q) for p, q in zip(a, b))
 
 
+def test_rotation_half_is_the_position_step_at_four_classes(dev):
+    """Both posteriors of da_d3pm_rot_step are one device routine (d3pm_categorical): da_d3pm_step at K = 4 on the rotation half's
+    rows and injected uniforms gives its rot_prev and post_rot bit for bit.  n = 9: a full workgroup and a one-row one; t mixes 0, the
+    ratio and large values."""
+    from diffassemble_amd import engine as E
+    n, K, steps, ratio = 9, 7, 600, 10
+    sch, _ = _sched(steps, dev)
+    gen = torch.Generator().manual_seed(4004)
+    logits, rl = (3.0 * torch.randn(n, K, generator=gen)).to(dev), (3.0 * torch.randn(n, 4, generator=gen)).to(dev)
+    x_t, r_t = torch.randint(0, K, (n,), generator=gen).to(dev), torch.randint(0, 4, (n,), generator=gen).to(dev)
+    u, ur = torch.rand(n, K, generator=gen).to(dev), torch.rand(n, 4, generator=gen).to(dev)
+    t = torch.tensor([0, ratio, 590, 337, 0, 599, ratio, 20, 0], device=dev)
+    _, _, rp, _, rpost = E.d3pm_rot_step(sch, x_t, r_t, logits, rl, t, ratio, noise_x=u, noise_rot=ur, return_post=True)
+    r4, post4 = E.d3pm_step(sch, r_t, rl, t, ratio, noise=ur, return_post=True)
+    assert torch.equal(r4, rp) and torch.equal(post4, rpost)
+    assert 0 <= int(rp.min()) and int(rp.max()) < 4 and bool(torch.isfinite(rpost).all())
+
+
 # ---------------------------------------------------------------------------------------- 2. the generator
 def test_rotation_draw_domain(dev):
     from diffassemble_amd import engine as E

@@ -157,6 +157,38 @@ def test_two_head_loss_is_finite_at_logit_scale_30(dev, K):
     _check_loss(dev, K, 63, 30.0, K, "scale 30")
 
 
+@pytest.mark.parametrize("kind", RT.KINDS)
+@pytest.mark.parametrize("K", [2, 65, 1024])
+def test_position_half_is_the_position_models_loss_row(dev, K, kind):
+    """da_d3pm_loss and the position half of da_d3pm_rot_loss run one device routine (d3pm_loss_row) and differ in one argument, the
+    label smoothing: 0.01 in every kind for the position model, 0.01 under "hybrid" and 0 otherwise for this one (RT.smoothing).
+    "hybrid" (same smoothing): the logit gradient, both row-term columns and the loss parts are equal bit for bit.
+    "vb" (the ce row is not used: weight 0, its loss part reads 0): the gradient, the loss parts and the vb column are equal bit for
+    bit; the unused ce column holds the smoothed cross entropy there and the plain one here, so it DIFFERS from this model's "vb"
+    column and equals its "hybrid" column bit for bit.
+    "cross_entropy" (smoothed there, plain here): the ce parts DIFFER -- the smoothing argument is wired, not ignored.
+    row_mix's period of 8 gives every t in {0, 1, mid, last} with x_t == x_0 and x_t != x_0; n = 9 ends in a one-row workgroup;
+    K = 2 has the empty "neither" class, K = 65 a second stride with one live lane."""
+    from diffassemble_amd.engine import d3pm_loss, d3pm_rot_loss
+    sch = sched_for(dev, RT.Q_STEPS)
+    logits, x0, xt, rl, r0, rt, t = (v.to(dev) for v in RT.row_mix(9, K, RT.Q_STEPS, seed=31 * K))
+    loss, d_logits, rows = d3pm_loss(sch, logits, x0, xt, t, kind=kind, lambda_loss=RT.LAMBDA)
+    loss_r, d_logits_r, _, rows_r = d3pm_rot_loss(sch, logits, rl, x0, xt, r0, rt, t, kind=kind, lambda_loss=RT.LAMBDA)
+    ce_gap = float((rows[:, 1] - rows_r[:, 1]).abs().max())
+    if kind == "cross_entropy":
+        assert float(loss[2]) != float(loss_r[3]) and not torch.equal(rows[:, 1], rows_r[:, 1]), (loss.tolist(), loss_r.tolist(), ce_gap)
+        return
+    assert torch.equal(d_logits, d_logits_r), float((d_logits - d_logits_r).abs().max())
+    assert torch.equal(loss, loss_r[[0, 2, 3]]), (loss.tolist(), loss_r.tolist())
+    assert torch.equal(rows[:, 0], rows_r[:, 0]), float((rows[:, 0] - rows_r[:, 0]).abs().max())
+    if kind == "hybrid":
+        assert torch.equal(rows[:, 1], rows_r[:, 1]), ce_gap
+    else:
+        assert RT.smoothing("vb")[0] == 0.0 and not torch.equal(rows[:, 1], rows_r[:, 1])
+        rows_h = d3pm_rot_loss(sch, logits, rl, x0, xt, r0, rt, t, kind="hybrid", lambda_loss=RT.LAMBDA)[3]
+        assert torch.equal(rows[:, 1], rows_h[:, 1]), float((rows[:, 1] - rows_h[:, 1]).abs().max())
+
+
 # ------------------------------------------------------------------------------------------------ denoiser forward + backward
 def make_backbone(c, dev):
     from diffassemble_amd.model.backbones import Eff_GAT_Discrete_ROT

@@ -2,7 +2,7 @@
 2D DDPM loop's (da_sample_loop_ex) for the same Batch, measured in the same process: 64 complete 144-piece puzzles (K = 144), bf16.
 
 The continuous step is the yardstick: the two loops share the denoiser body; the discrete one swaps the pose MLP for the embedding
-lookup (k_embed_idx_time) and the pose head + DDPM update for the tail kernel (k_d3pm_tail: K-wide head, softmax, posterior, Gumbel
+lookup (k_embed_idx_time_rot without its addend rows) and the pose head + DDPM update for the tail kernel (k_d3pm_tail: K-wide head, softmax, posterior, Gumbel
 term from the in-kernel generator, argmax).  Each loop runs once as warm-up (it records the hipGraph), then ``--reps`` replays of a
 ``--steps / --ratio``-iteration loop between two device events; a line reports the mean per iteration.  Synthetic seeded weights /
 inputs (oracle/weights.py, tests/golden/discrete_cases.py).  One JSON line per loop, then their difference.
