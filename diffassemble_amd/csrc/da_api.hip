@@ -1,15 +1,13 @@
-// C-ABI entry points of libdiffassemble_hip.so (include/diffassemble_hip.h).
+// C-ABI entry points of libdiffassemble_hip.so (include/diffassemble_hip.h), and the recording and caching of the loops' graphs.
+// The denoiser's record is da_denoiser.h; its weights are built in da_denoiser_create.hip, one forward is da_forward.hip.
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
 
 #include <utility>
-#include <vector>
 
-#include "da_common.h"
-#include "da_internal.h"
-#include "da_config.h"
+#include "da_denoiser.h"
 
 namespace da {
 
@@ -22,31 +20,6 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
-struct ConvW {
-    void *w = nullptr;     // [4*HC, Din] act dtype, rows = Q | K | V | skip
-    float *b = nullptr;    // [4*HC] fp32
-    // the same projection for the matrix-core attention kernels (da_attn_dense.hip / da_attn_dual.hip): the Q rows and
-    // biases are PRE-SCALED by log2(e) / sqrt(C), so that the kernels' scores arrive in log2 units and exp2 applies to them
-    // directly -- the softmax scale costs no instruction per score (scaled in fp32, before the rounding to the act dtype)
-    void *wd = nullptr;
-    float *bd = nullptr;
-    void *wdp = nullptr;   // wd in the fragment order of the row-panel projection kernel (da_gemm_xpanel.hip), bf16 only
-    void *wqs = nullptr;   // wd as per-head MFMA fragments (pack_w_qs): hidden layers whose attention kernel does the projection itself
-    int din = 0, hc = 0, C = 0;
-};
-
-// p[r][c] *= s for r < rows, c < cols (row pitch ld): scales the Q block of a packed projection in fp32
-__global__ void k_scale_block(float *p, int rows, int cols, int ld, float s) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (size_t)rows * cols) p[(i / cols) * ld + (i % cols)] *= s;
-}
-static int scale_block(float *p, int rows, int cols, int ld, float s, hipStream_t st) {
-    const size_t n = (size_t)rows * cols;
-    if (!n) return 0;
-    k_scale_block<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(p, rows, cols, ld, s);
-    DA_LAUNCH_CHECK();
-    return 0;
-}
 // dst[r][c] = bias[c] in the activation dtype (the feature share of mlp.0 for zero features)
 __global__ void k_fill_bias_rows(int prec, int rows, int cols, const float *bias, void *dst) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -59,182 +32,6 @@ __global__ void k_cfg_combine(size_t n, float wgt, float *cond, const float *unc
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) cond[i] = (1.0f + wgt) * cond[i] - wgt * unc[i];
 }
-static bool q_prescale_on() { return !(cfg().disable_folds & DA_FOLD_QSCALE); }
-static float q_scale_log2(int C) { return 1.4426950408889634f / sqrtf((float)C); }
-
-struct LoopKey {
-    da_graph g;
-    da_schedule s;
-    int mean_type, ratio, max_iters;
-    const float *x_init;
-    float *traj, *x_final;
-    void *ws;
-    size_t ws_bytes;
-    da_loop_opts opts;        // zero for the plain DDIM loop
-    size_t traj_stride;       // elements between consecutive iterations of `traj` (0 = n_real * c)
-    size_t noise_stride;      // the same for opts.noise (two-branch loops read row ranges of one [n_iters, N, c] buffer)
-    da_config cfg;            // the switches the graph was recorded under (da_config_set between two calls records a new graph)
-    const void *seed;         // da_sample_loop_idx: the device {seed, offset} pair the recorded kernels read (NULL otherwise)
-    // da_sample_loop_rot (mean_type -2): the rotation side's pointers and the cold switch (zero otherwise)
-    const void *rot_init, *rot_traj, *rot_final, *x_fixed, *noise_rot;
-    int cold;
-};
-
-}  // namespace da
-
-using namespace da;
-
-struct da_denoiser {
-    int prec = 0, variant = 0, arch = 0, steps = 0, c_in = 0, c_out = 0, F = 0, D = 0, hidden = 0, heads = 0,
-        n_layers = 0, V = 0, head_hidden = 0;
-    float *time_emb = nullptr, *pos_w0 = nullptr, *pos_b0 = nullptr, *pos_w1 = nullptr, *pos_b1 = nullptr;
-    void *mlp_w0 = nullptr, *mlp_w1 = nullptr;
-    float *mlp_b0 = nullptr, *mlp_b1 = nullptr;
-    ConvW conv[DA_MAX_LAYERS];
-    void *virt_emb = nullptr;
-    void *head_w0 = nullptr;
-    float *head_b0 = nullptr;
-    float *head_w1 = nullptr, *head_b1 = nullptr, *head_r_w1 = nullptr, *head_r_b1 = nullptr;
-    // 2D transformer arch: mlp.2 has no activation, so it is composed into its two consumers once per
-    // checkpoint (see da_denoiser_create): conv-0 projection over the 128-wide hidden layer, and the residual's
-    // share of final_mlp.0 as a pre-activation addend -- `combined` [N, 1152] is never materialised
-    bool fused_mlp2 = false;
-    void *conv0c_w = nullptr;         // [4*HC0, hidden] act dtype = Wcat0 . W2
-    float *conv0c_b = nullptr;        // [4*HC0] = Wcat0 . b2 + bcat0
-    void *headc_w = nullptr;          // [32, hidden] act dtype = Wf0 . W2
-    float *headc_b = nullptr;         // [32] = Wf0 . b2
-    void *virt_qkvs = nullptr;        // exophormer: [V, 4*HC0] act dtype = virt_emb . Wcat0^T + bcat0 (constant per checkpoint)
-    void *conv0c_wd = nullptr, *virt_qkvs_d = nullptr;      // their dense-path variants (Q pre-scaled, see ConvW)
-    void *conv0c_wdp = nullptr, *convLf_wp = nullptr;       // conv0c_wd / convLf_w packed for the row-panel kernel (see ConvW::wdp)
-    // disable_folds bit 256 (DA_FOLD_LAST_QPROJ) was clear when this denoiser was created: the folded last layer of complete graphs projects Q in the prologue
-    // of its attention kernel (k_attn_optt<144, true, false, .., 8192>), the projection kernel in front of it writes the K | V' columns only
-    bool last_qproj = false;
-    long owner_pid = 0;               // the process that created this denoiser: a forked child holds a copy of the handle but no HIP context (da_denoiser_destroy)
-    void *convLf_wp_kv = nullptr;     // rows HC .. of convLf_w (K | V') packed for the row-panel kernel
-    void *convLf_wq = nullptr;        // pack_w_qlast image of rows 0 .. HC - 1 (Q)
-    void *conv0c_wqs = nullptr;                             // conv0c_wd's per-head fragments (see ConvW::wqs)
-    bool attn_qsf = false;            // disable_folds bit 64 was clear when this denoiser was created: the wqs images exist, hidden layers of large complete
-                                      // graphs are projected by their attention kernel (a later da_config_set changes neither)
-    bool attn_x_fm = false;           // ... and disable_folds bit 128 (DA_FOLD_X_FM) was clear too: two such layers in a row hand their rows over fragment-major
-    float *conv0c_bd = nullptr;
-    bool q_prescaled = false;
-    // ... and the LAST conv's value / skip projections are folded with final_mlp.0 (its consumer, linear up to
-    // the GELU): softmax(QK^T)(V Wf_h^T) == (softmax(QK^T) V) Wf_h^T per head, so the last attention runs with
-    // 32-wide value heads and the [N, 1152] tensor z is never formed either (dense path only)
-    bool lastfold = false;
-    bool dense_only = false;     // every layer can take the block-diagonal MFMA attention: complete graphs never touch the CSR arrays
-    void *convLf_w = nullptr;         // [2*HC + H*32, 256] act dtype: Wq | Wk | (Wf_h Wv_h)_h
-    float *convLf_b = nullptr;        // [2*HC + H*32]
-    void *skipc_w = nullptr;          // [32, 256] act dtype = Wf0 . Ws_last
-    float *skipc_b = nullptr;         // [32] = Wf0 . bs_last + bf0
-    std::vector<void *> owned;
-    // optional per-kernel-class timing with HIP events (da_profile_*)
-    bool prof_on = false;
-    std::vector<hipEvent_t> prof_ev;      // pairs (start, stop)
-    std::vector<int> prof_cls;
-    size_t prof_used = 0;
-    // cached sampling-loop graphs (a few distinct loops, e.g. a full loop and a remainder), oldest first.  One entry type for both caches:
-    // a one-branch loop leaves `b` zero and `exec_b` null; a pair loop in split mode keeps its second branch as a graph of its own in `exec_b`
-    struct LoopEntry { LoopKey a, b; hipGraphExec_t exec, exec_b; };
-    std::vector<LoopEntry> loops;
-    hipStream_t cap_stream = nullptr;     // private stream used only to RECORD graphs (the caller's
-                                          // stream may be the legacy null stream, which cannot capture)
-    // hybrid graphs: the virtual rows of a hidden layer (one 16-wave workgroup per row, latency-bound, 256 rows
-    // for 32 puzzles) run on this side stream UNDER the masked MFMA attention of the real rows -- the two
-    // kernels read the same Q / K / V and write disjoint rows.  Fork / join with events, so the pattern is
-    // captured into the sampling-loop hipGraph as two parallel branches.
-    hipStream_t side_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // (round 6, measured: a SECOND side stream for the second branch of two Batches in flight makes configuration 3 slower -- x0.98 against
-    //  x1.14 - 1.25 with this one shared; small Batches do not fork at all, see forward_impl)
-    // da_sample_loop_pair: the second branch of the two-branch loop graph
-    hipStream_t pair_stream = nullptr;
-    hipEvent_t ev_pair_fork = nullptr, ev_pair_join = nullptr;
-    std::vector<LoopEntry> pair_loops;
-};
-
-namespace da {
-
-struct Workspace {
-    char *comb_in, *h, *combined, *qkvs, *xa, *xb, *z, *hh;
-    char *hh_unc, *pz_unc, *head_pre_unc;   // discrete variant: the unconditional pass's head rows (guidance: both passes' rows feed ONE tail kernel)
-    void *pz;                         // [H, n_real, 32] act dtype: per-head outputs of the folded last attention
-    char *head_pre;                   // [n_real, 32] act dtype: residual share of final_mlp.0 (fused_mlp2)
-    char *feat_proj;                  // [n_real, hidden] act dtype: mlp.0 over the piece-feature columns (+ bias), once per Batch
-    char *feat_proj_unc;              // the same for ZERO features (= the bias, broadcast): the unconditional pass of classifier-free guidance
-    char *feat_proj4;                 // DA_VARIANT_DISCRETE_ROT: the four rotated crops' feat_proj images [4][proj4_stride elements]; a step copies
-    size_t proj4_stride;              // row rot_acc[piece] of them into feat_proj (k_embed_idx_time_rot)
-    float *model_out_unc;
-    char *dq, *dk, *dvt, *dskip;      // dense path: head-major Q, K, V ([H][n_pad][C] each), row-major skip
-    size_t dense_off, dense_bytes;    // [dq, dq + dense_bytes) is zero-filled once per Batch
-    unsigned *virt_cnt;               // hybrid graphs with virtual rows: arrival counters of the rows' workgroups (inside the zero-filled region) ...
-    float *virt_part;                 // ... and their partial softmax states (AttnDenseParams::v_cnt / v_part)
-    float *model_out, *xbuf0, *xbuf1;
-    float *gcn_dinv;                  // GCN arch, CSR plans: deg^-1/2 per node (da_gcn.hip), once per Batch
-    size_t total;
-};
-
-static Workspace carve(const da_denoiser *d, const da_graph *g, void *base) {
-    const size_t s = esize(d->prec);
-    const size_t n = (size_t)g->n_nodes, nr = (size_t)g->n_real;
-    const size_t nrp = nr + 64, np = n + 64;          // slack rows so tile kernels may over-read
-    char *p = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *q = p ? p + off : nullptr;
-        off += align_up(bytes, 256);
-        return q;
-    };
-    Workspace w;
-    int hcmax = 0;
-    for (int l = 0; l < d->n_layers; ++l) hcmax = d->conv[l].hc > hcmax ? d->conv[l].hc : hcmax;
-    w.comb_in = take(nrp * d->D * s);
-    w.h = take(nrp * d->hidden * s);
-    w.feat_proj = take(nrp * d->hidden * s);
-    w.feat_proj_unc = take(nrp * d->hidden * s);
-    const bool rotv = d->variant == DA_VARIANT_DISCRETE_ROT;
-    w.head_pre = take(nrp * (rotv ? 64 : 32) * s);
-    w.pz = take(nrp * 32 * (size_t)d->heads * sizeof(float));
-    w.combined = take(np * d->D * s);
-    const bool gcn = d->arch == DA_ARCH_GCN;           // (the GCN reads none of the attention buffers: xa / xb / z / combined only)
-    w.qkvs = take(gcn ? 0 : np * 4 * (size_t)hcmax * s);
-    // (hidden layers' rows; fragment-major between two layers projected by their attention kernel, run_forward: n_pad rows of padded slots then)
-    const size_t nx = (g->dense || g->hybrid) && (size_t)g->n_pad > np ? (size_t)g->n_pad : np;
-    w.xa = take(nx * 256 * s);
-    w.xb = take(nx * 256 * s);
-    w.z = take(np * d->D * s);
-    w.hh = take(nrp * d->head_hidden * s);
-    const bool disc = d->variant == DA_VARIANT_DISCRETE;
-    w.hh_unc = take(disc ? nrp * d->head_hidden * s : 0);
-    w.pz_unc = take(disc ? nrp * 32 * (size_t)d->heads * sizeof(float) : 0);
-    w.head_pre_unc = take(disc ? nrp * 32 * s : 0);
-    w.dq = w.dk = w.dvt = w.dskip = nullptr;
-    w.virt_cnt = nullptr; w.virt_part = nullptr;
-    w.dense_off = off;
-    w.dense_bytes = 0;
-    if ((g->dense || g->hybrid) && g->n_pad > 0 && !gcn) {
-        const size_t hb = ((size_t)g->n_pad + 64) * hcmax * s;
-        w.dq = take(hb);
-        w.dk = take(hb);
-        w.dvt = take(hb);
-        if (g->hybrid && n > nr) w.virt_cnt = (unsigned *)take((n - nr) * sizeof(unsigned));
-        w.dense_bytes = off - w.dense_off;
-        if (g->hybrid && n > nr) w.virt_part = (float *)take((n - nr) * (size_t)DA_VIRT_SPLIT_MAX * 64 * 6 * sizeof(float));
-        w.dskip = take(np * (size_t)hcmax * s);
-    }
-    const int cpose = d->variant == DA_VARIANT_3D ? 7 : d->c_out;
-    w.model_out = (float *)take(nr * cpose * sizeof(float));
-    w.model_out_unc = (float *)take(nr * cpose * sizeof(float));
-    w.xbuf0 = (float *)take(nr * 8 * sizeof(float));
-    w.xbuf1 = (float *)take(nr * 8 * sizeof(float));
-    w.gcn_dinv = d->arch == DA_ARCH_GCN ? (float *)take(n * sizeof(float)) : nullptr;
-    w.proj4_stride = align_up(nrp * d->hidden * s, 256) / s;
-    w.feat_proj4 = take(rotv ? 4 * w.proj4_stride * s : 0);
-    w.total = off;
-    return w;
-}
-
-static bool mfma_disabled() { return cfg().disable_mfma != 0; }
 
 int linear(int prec, int M, int K, int Nout, const void *A, int lda, const void *W, const float *bias, int act,
            const void *res, void *out, int ldo, hipStream_t st) {
@@ -245,23 +42,9 @@ int linear(int prec, int M, int K, int Nout, const void *A, int lda, const void 
     return launch_gemm_simple(prec == DA_PREC_F32_BF16MMA ? DA_PREC_F32 : prec, M, K, Nout, A, lda, W, bias, act, res, out, ldo, st);
 }
 
-static bool dense_disabled() { return cfg().disable_dense != 0; }
-
-// The large-Batch step rule (da_config.xpanel = tail_next = -1): row-panel projections + the next step's embedding inside the tail kernel for
-// Batches whose largest graph has >= 512 pieces (round 5) OR that hold >= 16 384 pieces in all (round 6: tools/ab_config.py on configuration 2,
-// 512 puzzles of 144 pieces -- -6.9 % at 20-step loops, -4.0 % at 100, twelve of twelve interleaved pairs each; round 5's process-level A/B had
-// read that Batch as a loss).  Small Batches (the scripted 8-puzzle ones) keep the old path: nothing to gain from a panel of nine row tiles.
-static bool step_rule_batch(const da_graph *g) { return g->max_graph_nodes >= 512 || g->n_real >= 16384; }
-
 static bool stream_is_capturing(hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     return hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
-}
-
-static bool dense_ok(const da_graph *g, int heads, int C) {
-    const bool hyb = g->hybrid && g->mask && g->mask_ptr && g->irr_row_ptr;
-    return !dense_disabled() && (g->dense || hyb) && g->n_pad > 0 && g->graph_ptr && g->pad_ptr && g->row_map && heads == 8 &&
-           (C == 32 || C == 144) && !mfma_disabled();
 }
 
 static int check_graph(const da_denoiser *d, const da_graph *g) {
@@ -276,359 +59,9 @@ static int check_graph(const da_denoiser *d, const da_graph *g) {
     return 0;
 }
 
-// Bracket one launch with a (start, stop) event pair on the launch stream when profiling.
-template <typename F>
-static int timed(da_denoiser *d, int cls, hipStream_t st, F &&launch) {
-    if (!d->prof_on) return launch();
-    if (d->prof_used + 2 > d->prof_ev.size()) {
-        for (int k = 0; k < 2; ++k) {
-            hipEvent_t e;
-            DA_CHECK_HIP(hipEventCreate(&e));
-            d->prof_ev.push_back(e);
-        }
-    }
-    hipEvent_t a = d->prof_ev[d->prof_used], b = d->prof_ev[d->prof_used + 1];
-    DA_CHECK_HIP(hipEventRecord(a, st));
-    int rc = launch();
-    DA_CHECK_HIP(hipEventRecord(b, st));
-    d->prof_used += 2;
-    d->prof_cls.push_back(cls);
-    return rc;
-}
-
-// The discrete variant's inputs (da_d3pm.hip): position indices where the poses were; forward_impl then stops behind final_mlp.0 and
-// leaves its post-GELU rows in `hh` -- the K-wide head belongs to the tail kernel, which the caller launches.
-// With the last-layer fold the rows stay one step earlier: per-head outputs `pz` of the folded attention and the pre-activation addend
-// `pre` (hh = GELU(pre + sum_h pz_h), formed by the tail kernel as k_head_fold forms it); `folded` says which form this pass left.
-struct DiscreteIn {
-    const int32_t *idx;     // [n_real]
-    char *hh;               // [n_real, 32] act dtype
-    char *pz, *pre;         // [H, n_real, 32], [n_real, 32] act dtype
-    int folded;             // out
-    int rot = 0;            // DA_VARIANT_DISCRETE_ROT: hh is [n_real, 64], and the embedding selects the piece's feat_proj row by rot_acc
-    const int32_t *rot_acc = nullptr;       // [n_real] or NULL = image 0
-    D3pmRows rows() const { D3pmRows r; if (folded) { r.pz = pz; r.pre = pre; } else r.hh = hh; return r; }
-};
-
-static int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const int64_t *t, int64_t t_scalar,
-                        float *out, float *alpha, int alpha_all, float *pre_head, const Workspace &w,
-                        hipStream_t st, DdimFuse *ddim = nullptr, bool uncond = false, bool h_ready = false,
-                        DiscreteIn *disc = nullptr) {
-    const int prec = d->prec, nr = g->n_real, n = g->n_nodes, D = d->D;
-    int rc;
-    // (a-3) embedding: pose MLP + learned timestep lookup into the concat buffer, then mlp
-    // (h_ready: the previous step's tail kernel already wrote this step's w.h -- DdimFuse::nx_*, sampling loops only)
-    // exophormer, dense / hybrid path: the virtual rows' constant conv-0 projections are placed by extra workgroups of the embedding's launch (they
-    // depend on nothing of this step; the layer-0 code below skips its launch_scatter_virtual then)
-    VirtScatter vsc;
-    bool virt_scattered = false;
-    if (!h_ready && d->fused_mlp2 && n > nr && !alpha && w.dq && d->virt_qkvs_d && dense_ok(g, d->heads, d->conv[0].C) && DA_XENV("DA_VIRT_SCATTER_IN_EMBED", 1)) {
-        vsc.rows = n - nr; vsc.V = d->V; vsc.H = d->heads; vsc.C = d->conv[0].C; vsc.n_real = nr; vsc.n_pad = g->n_pad;
-        vsc.src = d->virt_qkvs_d; vsc.row_map = g->row_map; vsc.Q = w.dq; vsc.K = w.dk; vsc.Vt = w.dvt; vsc.S = w.dskip;
-        virt_scattered = true;
-    }
-    if (disc) {
-        disc->folded = 0;
-        if ((rc = timed(d, DA_PROF_EMBED, st, [&] {
-                 if (disc->rot)
-                     return launch_embed_idx_time_rot(prec, nr, d->c_out, d->F, D, d->hidden, disc->idx, disc->rot_acc, t, t_scalar, d->steps, d->time_emb,
-                                                      d->pos_w1, w.comb_in, w.feat_proj4, w.proj4_stride, w.feat_proj, st);
-                 return launch_embed_idx_time(prec, nr, d->c_out, d->F, D, disc->idx, t, t_scalar, d->steps, d->time_emb, d->pos_w1, w.comb_in, st); }))) return rc;
-    } else
-    if (!h_ready && (rc = timed(d, DA_PROF_EMBED, st, [&] {
-             return launch_embed_pos_time(prec, nr, d->c_in, d->F, D, x, t, t_scalar, d->steps, d->time_emb,
-                                          d->pos_w0, d->pos_b0, d->pos_w1, d->pos_b1, w.comb_in, st, virt_scattered ? &vsc : nullptr); }))) return rc;
-    const int act1 = d->variant == DA_VARIANT_3D ? DA_ACT_LEAKY02 : DA_ACT_GELU;
-    const int act2 = d->variant == DA_VARIANT_3D ? DA_ACT_LEAKY02 : DA_ACT_NONE;
-    // mlp.0 over [features | pose | time]: the feature columns (F of the D inputs) do not change inside a
-    // sampling loop, so their part of the product (+ bias) was computed once in da_denoiser_set_features;
-    // per step only the 64 pose / timestep columns are multiplied and the cached part is added before the
-    // activation (the reference recomputes the whole Linear(1152 -> 128) every step)
-    if (!h_ready && (rc = timed(d, DA_PROF_LINEAR_MLP, st, [&] {
-             const size_t es_ = esize(prec);
-             int r2 = mfma_disabled() ? -1
-                                      : launch_gemm_mfma(prec, nr, D - d->F, d->hidden, w.comb_in + (size_t)d->F * es_, D,
-                                                         (const char *)d->mlp_w0 + (size_t)d->F * es_, nullptr, act1, nullptr,
-                                                         w.h, d->hidden, nullptr, st, D, uncond ? w.feat_proj_unc : w.feat_proj);
-             if (r2 >= 0) return r2;
-             if (uncond) { set_error("unconditional pass: the hoisted mlp.0 path is not available for this shape"); return 1; }
-             if (disc && disc->rot) { set_error("discrete rot: the hoisted mlp.0 path is not available for this shape"); return 1; }
-             return linear(prec, nr, D, d->hidden, w.comb_in, D, d->mlp_w0, d->mlp_b0, act1, nullptr, w.h, d->hidden, st); }))) return rc;
-    // mlp.2 (Linear(128 -> 1152), no activation in 2D) only feeds two linear consumers -- the conv-0 projection
-    // and, through the residual, final_mlp.0 -- so for the transformer arch it is folded into their weights at
-    // create time: the [N, 1152] `combined` tensor is never written, conv 0 reduces over 128 instead of 1152
-    const bool fused = d->fused_mlp2;
-    if (!fused && (rc = timed(d, DA_PROF_LINEAR_MLP, st, [&] {
-             return linear(prec, nr, d->hidden, D, w.h, d->hidden, d->mlp_w1, d->mlp_b1, act2, nullptr, w.combined, D, st); }))) return rc;
-    // (a-4..a-6) graph transformer: fused Q|K|V|skip projection + attention per layer
-    const void *xin = fused ? w.h : w.combined;
-    int ldx = fused ? d->hidden : D;
-    // Whether layer l, fed rows of length ldx_in, is projected by its own attention kernel (k_attn_res<.., 64>: no projection kernel, K | V never
-    // leave the CU).  ONE predicate, asked twice: for the layer at hand, and one layer ahead -- two such layers in a row hand their rows over
-    // fragment-major (x_fm below), and the layer that writes them has to know what its reader will be.
-    auto layer_qsf = [&](int l, int ldx_in) -> bool {
-        if (l < 0 || l >= d->n_layers - 1 || d->arch == DA_ARCH_GCN) return false;          // (the last layer has its own kernels)
-        const ConvW &c = d->conv[l];
-        const int din = (fused && l == 0) ? d->hidden : c.din;
-        const void *wqs = (fused && l == 0) ? d->conv0c_wqs : c.wqs;
-        const bool virt0 = fused && l == 0 && n > nr, al = alpha && alpha_all;
-        if (al || !w.dq || !dense_ok(g, d->heads, c.C)) return false;
-#ifdef DA_EXPERIMENTS
-        if (g->dense && !g->hybrid && n == nr && conv_fused_applicable(prec, d->heads, c.C, din, g->max_graph_nodes, c.hc)) return false;
-#endif
-        return !g->hybrid && !virt0 && n == nr && wqs && ldx_in == din &&
-               attn_qsf_applicable(prec, d->heads, c.C, din, g->n_graphs, g->max_graph_nodes, g->n_pad, d->q_prescaled);
-    };
-    bool x_fm = false;          // xin is fragment-major over the padded slots (written so by the previous layer's attention kernel)
-    if (d->arch == DA_ARCH_GCN) {
-        // backbones/gcn.py:16-22, gelu(conv1(gelu(conv0(x)))), reassociated so that both aggregations run 256 wide:
-        // conv 0 projects first (A_hat (X W0^T)), conv 1 aggregates first ((A_hat H) W1^T); the residual `feats + combined_feats`
-        // (efficient_gat.py:144 / efficient_gat_3d.py:199) is added in the epilogue of conv 1's GEMM, after its GELU
-        const ConvW &c0 = d->conv[0], &c1 = d->conv[1];
-        const int hid = c0.hc;
-        if ((rc = timed(d, DA_PROF_LINEAR_QKVS, st, [&] {
-                 return linear(prec, nr, D, hid, w.combined, D, c0.w, nullptr, DA_ACT_NONE, nullptr, w.xa, hid, st); }))) return rc;
-        if ((rc = timed(d, DA_PROF_ATTN_HIDDEN, st, [&] {
-                 return launch_gcn_aggregate(prec, g, hid, w.gcn_dinv, w.xa, c0.b, DA_ACT_GELU, w.xb, st); }))) return rc;
-        if ((rc = timed(d, DA_PROF_ATTN_LAST, st, [&] {
-                 return launch_gcn_aggregate(prec, g, hid, w.gcn_dinv, w.xb, nullptr, DA_ACT_NONE, w.xa, st); }))) return rc;
-        if ((rc = timed(d, DA_PROF_LINEAR_QKVS, st, [&] {
-                 return linear(prec, nr, hid, D, w.xa, hid, c1.w, c1.b, DA_ACT_GELU, w.combined, w.z, D, st); }))) return rc;
-    } else
-    for (int l = 0; l < d->n_layers; ++l) {
-        ConvW c = d->conv[l];
-        if (fused && l == 0) { c.w = d->conv0c_w; c.b = d->conv0c_b; c.din = d->hidden; }
-        // fused conv 0 of the exophormer arch: only the real rows go through the GEMM, the virtual rows'
-        // projections are constants that launch_scatter_virtual places behind them
-        const int nproj = (fused && l == 0) ? nr : n;
-        const bool virt0 = fused && l == 0 && n > nr;
-        const bool last = l == d->n_layers - 1;
-        void *dst = last ? (void *)w.z : (void *)((l & 1) ? w.xb : w.xa);
-        const int act = (!last && d->arch == DA_ARCH_TRANSFORMER) ? DA_ACT_GELU : DA_ACT_NONE;
-        float *al = !alpha ? nullptr
-                           : (alpha_all ? alpha + (size_t)l * g->n_edges * d->heads : (last ? alpha : nullptr));
-        // last layer: the residual `feats + combined_feats` (efficient_gat.py:144) is fused in the epilogue
-        const void *resid = (last && !fused) ? w.combined : nullptr;
-        if (last && fused && d->lastfold && !al && w.dq && (g->hybrid || d->V == 0) && dense_ok(g, d->heads, c.C)) {
-            // folded last layer: Q | K | (V Wf_h^T) projection, 32-wide value heads, per-head outputs to pz
-            QkvScatter qs;
-            qs.HC = c.hc; qs.C = c.C; qs.Cv = 32; qs.n_pad = g->n_pad; qs.row_map = g->row_map;
-            qs.Q = w.dq; qs.K = w.dk; qs.Vt = w.dvt; qs.S = nullptr;
-            // complete graphs (disable_folds bit 256 clear at creation): the K | V' columns only -- Q is projected by the attention kernel, per 32-query slab,
-            // in its prologue, and never exists in memory (45 % of this launch's stores, and the attention kernel's reads of them).  Hybrid graphs keep the
-            // three-block launch and the masked kernel.
-            const bool lq = d->last_qproj && !g->hybrid && n == nr && !x_fm &&
-                            attn_last_qproj_applicable(prec, d->heads, c.C, c.din, g->n_pad, d->q_prescaled);
-            if (lq) qs.col0 = c.hc;
-            rc = timed(d, DA_PROF_LINEAR_QKVS, st, [&] {
-                if (lq)
-                    return launch_gemm_mfma(prec, n, c.din, c.hc + d->heads * 32, xin, ldx, (const char *)d->convLf_w + (size_t)c.hc * c.din * esize(prec),
-                                            d->convLf_b + c.hc, DA_ACT_NONE, nullptr, nullptr, 0, &qs, st, 0, nullptr, d->convLf_wp_kv);
-                return launch_gemm_mfma(prec, n, c.din, 2 * c.hc + d->heads * 32, xin, ldx, d->convLf_w, d->convLf_b, DA_ACT_NONE,
-                                        nullptr, nullptr, 0, &qs, st, 0, nullptr, d->convLf_wp); });
-            if (rc > 0) return rc;
-            DA_REQUIRE(rc == 0 || !lq, "da_denoiser_forward: no projection kernel took the last layer's K | V' columns");
-            if (rc == 0) {
-                DenseLayout L;
-                L.Q = w.dq; L.K = w.dk; L.Vt = w.dvt; L.S = nullptr; L.n_pad = g->n_pad; L.q_prescaled = d->q_prescaled;
-                if (lq) { L.Q = nullptr; L.x = xin; L.ldx = ldx; L.kin = c.din; L.wqs = d->convLf_wq; L.bias = d->convLf_b; }
-                DenseFold fo;
-                fo.cv = 32; fo.out = disc ? (void *)disc->pz : w.pz; fo.n_rows = nr;
-                // hybrid graphs: adjacency-masked, remainder edges of the real rows folded in the epilogue; the
-                // virtual rows' outputs of the LAST layer are dropped by the model (exophormer_gnn.py:209), so the
-                // CSR-side kernels are not needed here
-                const DenseMask mk = dense_mask_of(g);
-                rc = timed(d, DA_PROF_ATTN_LAST, st, [&] {
-                    return launch_attn_dense(prec, L, d->heads, c.C, g->n_graphs, g->max_graph_nodes, g->graph_ptr,
-                                             g->pad_ptr, g->dense == 2, nullptr, DA_ACT_NONE, nullptr, st,
-                                             g->hybrid ? &mk : nullptr, &fo); });
-                if (rc > 0) return rc;
-                if (rc == 0 && disc) {
-                    // discrete variant: the addend of final_mlp.0 (mlp.2 share + skip share); the K-wide head is the tail kernel's
-                    if ((rc = timed(d, DA_PROF_HEAD, st, [&] {
-                             return linear(prec, nr, d->hidden, 32, w.h, d->hidden, d->headc_w, d->headc_b, DA_ACT_NONE, nullptr, disc->pre, 32, st); }))) return rc;
-                    if ((rc = timed(d, DA_PROF_HEAD, st, [&] {
-                             return linear(prec, nr, c.din, 32, xin, ldx, d->skipc_w, d->skipc_b, DA_ACT_NONE, disc->pre, disc->pre, 32, st); }))) return rc;
-                    disc->folded = 1;
-                    return 0;
-                }
-                if (rc == 0) {
-                    // the whole tail in one kernel where it is covered (bf16, hidden 128, conv input 256) ...
-                    {
-                        const bool fuse_ddim = ddim && d->c_out == d->c_in;
-                        int rt = -1;
-                        if ((rc = timed(d, DA_PROF_HEAD, st, [&] {
-                                 rt = launch_tail_fused(prec, nr, d->heads, d->c_out, d->hidden, c.din, w.h, xin, ldx, d->headc_w, d->headc_b,
-                                                        d->skipc_w, d->skipc_b, w.pz, d->head_w1, d->head_b1, out, st, fuse_ddim ? ddim : nullptr);
-                                 return rt > 0 ? rt : 0; }))) return rc;
-                        if (rt == 0) { if (fuse_ddim) ddim->done = 1; return 0; }
-                    }
-                    // ... else: pre-activation of final_mlp.0 from the hidden layer (mlp.2 share) and from this conv's input (skip share)
-                    if ((rc = timed(d, DA_PROF_HEAD, st, [&] {
-                             return linear(prec, nr, d->hidden, 32, w.h, d->hidden, d->headc_w, d->headc_b, DA_ACT_NONE, nullptr, w.head_pre, 32, st); }))) return rc;
-                    if ((rc = timed(d, DA_PROF_HEAD, st, [&] {
-                             return linear(prec, nr, c.din, 32, xin, ldx, d->skipc_w, d->skipc_b, DA_ACT_NONE, w.head_pre, w.head_pre, 32, st); }))) return rc;
-                    if (ddim && d->c_out == d->c_in) ddim->done = 1;        // the head kernel applies the DDIM update itself
-                    return timed(d, DA_PROF_HEAD, st, [&] {
-                        return launch_head_fold(prec, nr, d->heads, d->c_out, w.pz, w.head_pre, d->head_w1, d->head_b1, out, st,
-                                                (ddim && ddim->done) ? ddim : nullptr); });
-                }
-            }
-        }
-#ifdef DA_EXPERIMENTS          // (DA_CONV_FUSED=1: the one-kernel hidden conv, da_conv_fused.hip -- a measured tie / loss, experiments build only)
-        if (!al && !last && g->dense && !g->hybrid && n == nr && !resid && dense_ok(g, d->heads, c.C) &&
-            conv_fused_applicable(prec, d->heads, c.C, c.din, g->max_graph_nodes, c.hc)) {
-            // hidden conv on complete graphs: projection + attention of a (graph, head) in ONE kernel, K / V in LDS
-            rc = timed(d, DA_PROF_CONV_FUSED, st, [&] {
-                return launch_conv_fused(prec, d->heads, c.C, c.din, g->n_graphs, g->max_graph_nodes, g->graph_ptr,
-                                         g->dense == 2, xin, ldx, c.w, c.b, act, dst, c.hc, st); });
-            if (rc) return rc < 0 ? 1 : rc;
-            xin = dst; ldx = c.hc;
-            continue;
-        }
-#endif
-        if (!al && w.dq && dense_ok(g, d->heads, c.C)) {
-            // complete graphs: projection scattered into head-major Q / K / V, block-diagonal MFMA attention
-            QkvScatter qs;
-            qs.HC = c.hc; qs.C = c.C; qs.n_pad = g->n_pad; qs.row_map = g->row_map;
-            qs.Q = w.dq; qs.K = w.dk; qs.Vt = w.dvt; qs.S = w.dskip;
-            const void *wdense = (fused && l == 0) ? d->conv0c_wd : c.wd;
-            const float *bdense = (fused && l == 0) ? d->conv0c_bd : c.bd;
-            const int xpm = xpanel_mode();
-            const void *wpanel = (xpm == 1 || (xpm == 2 && step_rule_batch(g))) ? ((fused && l == 0) ? d->conv0c_wdp : c.wdp) : nullptr;
-            // Hidden layers of large complete graphs: the resident attention kernel (k_attn_res<.., 64>) does the layer's projection in its own
-            // prologue -- no projection kernel, K | V never leave the CU
-            const void *wqs = (fused && l == 0) ? d->conv0c_wqs : c.wqs;
-            const bool qsf = !resid && layer_qsf(l, ldx);
-            // ... and hands its rows to the next layer in MFMA operand order where that one is projected the same way (disable_folds bit 128 clear
-            // at creation): its prologue then reads 1 KB-contiguous fragments instead of 32-byte pieces of 64 rows.  Private between the two launches;
-            // the last hidden layer's rows stay row-major (the last layer's projection and the tail kernel read them)
-            const bool out_fm = qsf && d->attn_x_fm && layer_qsf(l + 1, c.hc);
-            DA_REQUIRE(!x_fm || qsf, "da_denoiser_forward: layer %d was handed fragment-major rows it does not take", l);
-            if (qsf) rc = 0; else
-            rc = timed(d, DA_PROF_LINEAR_QKVS, st, [&] {
-                return launch_gemm_mfma(prec, nproj, c.din, 4 * c.hc, xin, ldx, wdense, bdense, DA_ACT_NONE, nullptr, nullptr, 0, &qs, st, 0,
-                                        nullptr, wpanel); });
-            if (rc > 0) return rc;
-            if (rc == 0 && virt0 && !virt_scattered &&
-                (rc = launch_scatter_virtual(prec, n - nr, d->V, d->heads, c.C, d->virt_qkvs_d, nr, g->row_map, g->n_pad, w.dq, w.dk,
-                                             w.dvt, w.dskip, nullptr, st))) return rc;
-            if (rc == 0) {
-                DenseLayout L;
-                L.Q = w.dq; L.K = w.dk; L.Vt = w.dvt; L.S = w.dskip; L.n_pad = g->n_pad; L.q_prescaled = d->q_prescaled;
-                if (qsf) { L.x = xin; L.ldx = ldx; L.kin = c.din; L.wqs = wqs; L.bias = bdense; L.x_fm = x_fm; L.out_fm = out_fm; }
-                if (g->hybrid) {
-                    // sparse-but-heavy graphs: masked MFMA attention over the regular edges (partial softmax
-                    // state), then the remaining edges + normalisation + skip / activation on the CSR side
-                    DenseMask mk = dense_mask_of(g);
-                    // SMALL Batches (below 8 192 pieces: the ones that do not fork a side stream below): the virtual rows inside the masked
-                    // attention's own launch (bf16 hidden layers: k_attn_optt<32, false, true>; da_config disable_folds bit 5 keeps the two-kernel
-                    // form) -- the scripted 8-puzzle Batch 0.152 -> 0.114 ms per step, 0.085 -> 0.066 / 0.052 -> 0.043 per Batch-step with two /
-                    // four Batches in flight.  Large Batches keep the side stream: configuration 3 measured -2 % ... +4 % with the rows in the
-                    // launch, depending on where in the grid they sit (profiles/r06/r06_virtual_rows_in_launch_ab*.log).
-                    // (experiments build: DA_VIRT_IN_LAUNCH=0 two kernels everywhere, =2 in the launch for every Batch)
-                    int virt_taken = 0;
-                    [[maybe_unused]] const int vil = DA_XENV("DA_VIRT_IN_LAUNCH", 1);
-                    if (n > nr && !resid && w.virt_cnt && w.virt_part && !(cfg().disable_folds & DA_FOLD_HYBRID_OVERLAP) && vil && (g->n_real < 8192 || vil == 2)) {
-                        mk.v_rows = n - nr; mk.v_n_real = nr;
-                        mk.v_row_ptr = g->agg_row_ptr ? g->agg_row_ptr : g->irr_row_ptr; mk.v_col_src = g->agg_row_ptr ? g->agg_col_src : g->irr_col_src;
-                        mk.v_mult = g->agg_row_ptr ? g->agg_mult : nullptr;
-                        mk.v_part = w.virt_part; mk.v_cnt = w.virt_cnt; mk.v_taken = &virt_taken;
-                        rc = timed(d, last ? DA_PROF_ATTN_LAST : DA_PROF_ATTN_HIDDEN, st, [&] {
-                            return launch_attn_dense(prec, L, d->heads, c.C, g->n_graphs, g->max_graph_nodes, g->graph_ptr, g->pad_ptr, 0, resid, act, dst, st, &mk); });
-                        if (rc) return rc < 0 ? 1 : rc;
-                        if (!virt_taken) {          // (a kernel without the extra workgroups took the layer: the rows' own kernel behind it)
-                            rc = timed(d, last ? DA_PROF_ATTN_LAST : DA_PROF_ATTN_HIDDEN, st, [&] {
-                                return launch_attn_csr_cont(prec, n, nr, mk.v_row_ptr, mk.v_col_src, g->row_map, d->heads, c.C, g->n_pad, L, resid, act, dst, st, mk.v_mult); });
-                            if (rc) return rc < 0 ? 1 : rc;
-                        }
-                        xin = dst; ldx = c.hc;
-                        continue;
-                    }
-                    // (small Batches keep the virtual rows on the caller's stream: below ~8 k pieces the fork / join costs more than the overlap
-                    //  buys -- the scripted 8-puzzle Batch: 0.165 -> 0.152 ms per step, profiles/r06/r06_scripted_side_stream_variants.log)
-                    if (d->side_stream && !d->prof_on && n > nr && g->n_real >= 8192) {
-                        // fork: virtual rows on the side stream, real rows here, join before the next projection
-                        StreamJoin side_guard;      // the error exits below still join the side stream (a capture of `st` must not be left forked)
-                        DA_CHECK_HIP(hipEventRecord(d->ev_fork, st));
-                        DA_CHECK_HIP(hipStreamWaitEvent(d->side_stream, d->ev_fork, 0));
-                        side_guard.arm(d->side_stream, st, d->ev_join);
-                        rc = launch_attn_csr_cont(prec, n, nr, g->agg_row_ptr ? g->agg_row_ptr : g->irr_row_ptr, g->agg_row_ptr ? g->agg_col_src : g->irr_col_src,
-                                                  g->row_map, d->heads, c.C, g->n_pad, L, resid, act, dst, d->side_stream, g->agg_row_ptr ? g->agg_mult : nullptr);
-                        if (rc) return rc < 0 ? 1 : rc;
-                        DA_CHECK_HIP(hipEventRecord(d->ev_join, d->side_stream));
-                        rc = launch_attn_dense(prec, L, d->heads, c.C, g->n_graphs, g->max_graph_nodes, g->graph_ptr,
-                                               g->pad_ptr, 0, resid, act, dst, st, &mk);
-                        if (rc) return rc < 0 ? 1 : rc;
-                        DA_CHECK_HIP(hipStreamWaitEvent(st, d->ev_join, 0));
-                        side_guard.armed = false;   // joined above: ev_join was recorded behind the rows' kernel, before the real rows' launch
-                        xin = dst; ldx = c.hc;
-                        continue;
-                    }
-                    rc = timed(d, last ? DA_PROF_ATTN_LAST : DA_PROF_ATTN_HIDDEN, st, [&] {
-                        int r2 = launch_attn_dense(prec, L, d->heads, c.C, g->n_graphs, g->max_graph_nodes, g->graph_ptr,
-                                                   g->pad_ptr, 0, resid, act, dst, st, &mk);
-                        if (r2) return r2;
-                        return launch_attn_csr_cont(prec, n, nr, g->agg_row_ptr ? g->agg_row_ptr : g->irr_row_ptr, g->agg_row_ptr ? g->agg_col_src : g->irr_col_src,
-                                                    g->row_map, d->heads, c.C, g->n_pad, L, resid, act, dst, st, g->agg_row_ptr ? g->agg_mult : nullptr); });
-                    if (rc) return rc < 0 ? 1 : rc;
-                    xin = dst; ldx = c.hc;
-                    continue;
-                }
-                // (a layer projected by its attention kernel is ONE kernel: priced as such, projection + attention FLOP, Q | K | V | skip never in HBM)
-                rc = timed(d, qsf ? DA_PROF_CONV_FUSED : (last ? DA_PROF_ATTN_LAST : DA_PROF_ATTN_HIDDEN), st, [&] {
-                    return launch_attn_dense(prec, L, d->heads, c.C, g->n_graphs, g->max_graph_nodes, g->graph_ptr,
-                                             g->pad_ptr, g->dense == 2, resid, act, dst, st); });
-                if (rc > 0) return rc;
-                if (rc == 0) { xin = dst; ldx = c.hc; x_fm = out_fm; continue; }
-            }
-        }
-        DA_REQUIRE(!x_fm, "da_denoiser_forward: layer %d was handed fragment-major rows it does not take", l);
-        if ((rc = timed(d, DA_PROF_LINEAR_QKVS, st, [&] {
-                 return linear(prec, nproj, c.din, 4 * c.hc, xin, ldx, c.w, c.b, DA_ACT_NONE, nullptr, w.qkvs, 4 * c.hc, st); }))) return rc;
-        if (virt0 && (rc = launch_scatter_virtual(prec, n - nr, d->V, d->heads, c.C, d->virt_qkvs, nr, nullptr, 0, nullptr, nullptr,
-                                                  nullptr, nullptr, w.qkvs, st))) return rc;
-        DA_REQUIRE(g->row_ptr && (g->col_src || g->n_edges == 0), "da_graph: this call walks the edge list (alpha requested or no "
-                   "MFMA attention for this layer) but the CSR arrays are missing");
-        // tiny complete graphs at a head width without a matrix-core kernel (the 3D variant: 20-fragment objects, C = 104): one workgroup per graph
-        // with the graph's K | V rows in LDS instead of one walk of the edge list per destination
-        int tiny = -1;
-        if (!al && g->dense && n == nr && g->graph_ptr && !dense_disabled()) {
-            if ((rc = timed(d, last ? DA_PROF_ATTN_LAST : DA_PROF_ATTN_HIDDEN, st, [&] {
-                     tiny = launch_attn_tiny(prec, g->n_graphs, g->max_graph_nodes, g->graph_ptr, g->dense == 2, d->heads, c.C, w.qkvs, resid, act, dst, st);
-                     return tiny > 0 ? tiny : 0; }))) return rc;
-        }
-        if (tiny != 0 && (rc = timed(d, last ? DA_PROF_ATTN_LAST : DA_PROF_ATTN_HIDDEN, st, [&] {
-                 return launch_attn_csr(prec, n, g->row_ptr, g->col_src, g->edge_id, d->heads, c.C, w.qkvs,
-                                        resid, act, dst, al, nullptr, st); }))) return rc;
-        xin = dst;
-        ldx = c.hc;
-    }
-    // (a-7 / a-13) pose head
-    char *const hh = disc ? disc->hh : w.hh;
-    if (fused) {
-        // final_mlp.0(conv_out + combined) = Wf . conv_out + (Wf W2) . h + (Wf b2 + bf): the second term first
-        // (hw: 32 rows of final_mlp.0; the discrete rot variant runs final_mlp.0 | final_mlp_rot.0 as one 64-wide product, as the 3D heads do)
-        const int hw = d->variant == DA_VARIANT_DISCRETE_ROT ? 64 : 32;
-        if ((rc = timed(d, DA_PROF_HEAD, st, [&] {
-                 return linear(prec, nr, d->hidden, hw, w.h, d->hidden, d->headc_w, d->headc_b, DA_ACT_NONE, nullptr, w.head_pre, hw, st); }))) return rc;
-        rc = timed(d, DA_PROF_HEAD, st, [&] {
-            return launch_gemm_mfma(prec, nr, D, d->head_hidden, w.z, D, d->head_w0, d->head_b0, DA_ACT_GELU, nullptr, hh,
-                                    d->head_hidden, nullptr, st, D, w.head_pre); });
-        if (rc > 0) return rc;
-        DA_REQUIRE(rc == 0, "fused head GEMM: shape not supported");
-    } else if ((rc = timed(d, DA_PROF_HEAD, st, [&] {
-             return linear(prec, nr, D, d->head_hidden, w.z, D, d->head_w0, d->head_b0, DA_ACT_GELU, nullptr, hh,
-                           d->head_hidden, st); }))) return rc;
-    if (disc) return 0;
-    return timed(d, DA_PROF_HEAD, st, [&] {
-        if (d->variant == DA_VARIANT_3D)
-            return launch_head3d(prec, nr, hh, d->head_w1, d->head_b1, d->head_r_w1, d->head_r_b1, out, pre_head, st);
-        return launch_head2d(prec, nr, d->c_out, hh, d->head_w1, d->head_b1, out, st);
-    });
-}
-
 }  // namespace da
+
+using namespace da;
 
 // one wave that waits `ticks` of the 100 MHz real-time counter (phase-offset experiment of the two-branch loop)
 __global__ void k_pair_delay(unsigned long long ticks) {
@@ -773,259 +206,14 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
         DA_REQUIRE(!rotv || (w->head_w0 && w->head_b0 && w->head_r_w0 && w->head_r_b0 && w->head_r_w1 && w->head_r_b1),
                    "da_denoiser_create(discrete rot): head_w0 / head_b0 or head_r_w0 / head_r_b0 / head_r_w1 / head_r_b1 (final_mlp_rot) missing");
     }
-    hipStream_t st = (hipStream_t)stream;
     da_denoiser *d = new da_denoiser();
     d->owner_pid = (long)getpid();
     d->prec = precision; d->variant = w->variant; d->arch = w->arch; d->steps = w->steps; d->c_in = w->c_in;
     d->c_out = w->c_out; d->F = w->feat_dim; d->D = w->feat_dim + 64; d->hidden = w->hidden; d->heads = w->heads;
     d->n_layers = w->n_layers; d->V = w->arch == DA_ARCH_EXOPHORMER ? w->virt_nodes : 0;
     d->head_hidden = w->variant == DA_VARIANT_3D ? 512 : (rotv ? 64 : 32);
-    const int D = d->D, H = d->heads;
-    const size_t s = esize(precision);
-    int rc = 0;
-    auto fail = [&](int code) { da_denoiser_destroy(d); return code; };
-    auto alloc = [&](size_t bytes) -> void * {
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes < 256 ? 256 : bytes) != hipSuccess) { set_error("hipMalloc(%zu) failed", bytes); return nullptr; }
-        d->owned.push_back(p);
-        return p;
-    };
-    auto copy_f32 = [&](const float *src, size_t n) -> float * {
-        float *p = (float *)alloc(n * 4);
-        if (!p || hipMemcpyAsync(p, src, n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { rc = 2; return nullptr; }
-        return p;
-    };
-    auto pack = [&](const float *src, size_t n) -> void * {
-        void *p = alloc(n * s + 4096);       // slack: tile kernels may over-read a partial tile
-        if (!p || launch_convert(precision, n, src, p, st)) { rc = 2; return nullptr; }
-        return p;
-    };
-    // per-head Q / skip fragments of a hidden layer's dense-path projection (bf16, 32-wide heads, K = 128 / 256); nullptr otherwise
-    d->attn_qsf = attn_qsf_enabled();
-    d->attn_x_fm = d->attn_qsf && !(cfg().disable_folds & DA_FOLD_X_FM);
-    auto pack_qs = [&](const void *wsrc, int K, int hc, int C) -> void * {
-        if (!d->attn_qsf) return nullptr;
-        if (precision != DA_PREC_BF16 || C != 32 || H != 8 || (K != 128 && K != 256) || !wsrc || mfma_disabled()) return nullptr;
-        void *p = alloc(w_qs_bytes(H, K));
-        if (!p || pack_w_qs(H, K, hc, wsrc, p, st)) { rc = 2; return nullptr; }
-        return p;
-    };
-    // fragment-major copy of a projection weight for the row-panel kernel; nullptr when the shape has no packed form
-    auto pack_panel = [&](const void *wsrc, int K, int Nout) -> void * {
-        const size_t nb = xpanel_in_model() ? da_linear_packed_bytes(precision, K, Nout) : 0;
-        if (!nb || !wsrc) return nullptr;
-        void *p = alloc(nb);
-        if (!p || pack_w_xpanel(K, Nout, wsrc, K, p, st)) { rc = 2; return nullptr; }
-        return p;
-    };
-    d->time_emb = copy_f32(w->time_emb, (size_t)w->steps * 32);
-    if (discrete) {
-        d->pos_w1 = copy_f32(w->pos_w1, (size_t)w->c_out * 32);        // pos_mlp.weight [K, 32]; pos_w0 / pos_b0 / pos_b1 are not read
-    } else {
-        d->pos_w0 = copy_f32(w->pos_w0, 16 * (size_t)w->c_in); d->pos_b0 = copy_f32(w->pos_b0, 16);
-        d->pos_w1 = copy_f32(w->pos_w1, 32 * 16); d->pos_b1 = copy_f32(w->pos_b1, 32);
-    }
-    d->mlp_w0 = pack(w->mlp_w0, (size_t)d->hidden * D); d->mlp_b0 = copy_f32(w->mlp_b0, d->hidden);
-    d->mlp_w1 = pack(w->mlp_w1, (size_t)D * d->hidden); d->mlp_b1 = copy_f32(w->mlp_b1, D);
-    if (rc) return fail(rc);
-    if (d->arch == DA_ARCH_GCN) {
-        // GCNConv(D, 256), GCNConv(256, D) (gcn.py:9-14): lin.weight [out, in] packed in the act dtype (no bias in lin), bias fp32
-        for (int l = 0; l < 2; ++l) {
-            ConvW &c = d->conv[l];
-            c.din = l == 0 ? D : 256;
-            c.hc = l == 0 ? 256 : D;
-            if (!w->conv_wq[l] || !w->conv_bq[l]) { set_error("gcn conv %d: missing weight pointer", l); return fail(1); }
-            c.w = pack(w->conv_wq[l], (size_t)c.hc * c.din);
-            c.b = copy_f32(w->conv_bq[l], c.hc);
-            c.wd = c.w; c.bd = c.b;
-            if (rc) return fail(rc);
-        }
-    }
-    for (int l = 0; l < (d->arch == DA_ARCH_GCN ? 0 : d->n_layers); ++l) {
-        ConvW &c = d->conv[l];
-        c.din = l == 0 ? D : 32 * H;
-        c.C = l == d->n_layers - 1 ? D / H : 32;
-        c.hc = c.C * H;
-        const size_t blk = (size_t)c.hc * c.din;
-        char *wp = (char *)alloc(4 * blk * s + 4096);
-        c.b = (float *)alloc(4 * (size_t)c.hc * 4);
-        if (!wp || !c.b) return fail(2);
-        c.w = wp;
-        const float *ws[4] = {w->conv_wq[l], w->conv_wk[l], w->conv_wv[l], w->conv_ws[l]};
-        const float *bs[4] = {w->conv_bq[l], w->conv_bk[l], w->conv_bv[l], w->conv_bs[l]};
-        for (int k = 0; k < 4; ++k) {
-            if (!ws[k] || !bs[k]) { set_error("conv %d: missing weight pointer", l); return fail(1); }
-            if (launch_convert(precision, blk, ws[k], wp + k * blk * s, st)) return fail(2);
-            if (hipMemcpyAsync(c.b + (size_t)k * c.hc, bs[k], (size_t)c.hc * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-        }
-        c.wd = c.w; c.bd = c.b;
-        if (q_prescale_on()) {
-            char *wd = (char *)alloc(4 * blk * s + 4096);
-            float *tq = (float *)alloc(blk * 4);
-            c.bd = (float *)alloc(4 * (size_t)c.hc * 4);
-            if (!wd || !tq || !c.bd) return fail(2);
-            c.wd = wd;
-            if (hipMemcpyAsync(tq, ws[0], blk * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-            if (scale_block(tq, c.hc, c.din, c.din, q_scale_log2(c.C), st)) return fail(2);
-            if (launch_convert(precision, blk, tq, wd, st)) return fail(2);
-            if (hipMemcpyAsync(wd + blk * s, wp + blk * s, 3 * blk * s, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-            if (hipMemcpyAsync(c.bd, c.b, 4 * (size_t)c.hc * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-            if (scale_block(c.bd, 1, c.hc, c.hc, q_scale_log2(c.C), st)) return fail(2);
-        }
-        c.wdp = pack_panel(c.wd, c.din, 4 * c.hc);
-        if (l < d->n_layers - 1) c.wqs = pack_qs(c.wd, c.din, c.hc, c.C);
-        if (rc) return fail(rc);
-    }
-    d->q_prescaled = q_prescale_on();
-    if (d->V > 0) {
-        if (!w->virt_emb) { set_error("exophormer: virt_emb missing"); return fail(1); }
-        d->virt_emb = pack(w->virt_emb, (size_t)d->V * D);
-    }
-    float *hw0 = nullptr;                                  // discrete rot: the two first head layers stacked, fp32
-    if (d->variant == DA_VARIANT_3D) {
-        char *hp = (char *)alloc(512 * (size_t)D * s + 4096);
-        d->head_b0 = (float *)alloc(512 * 4);
-        if (!hp || !d->head_b0) return fail(2);
-        d->head_w0 = hp;
-        if (launch_convert(precision, 256 * (size_t)D, w->head_w0, hp, st)) return fail(2);
-        if (launch_convert(precision, 256 * (size_t)D, w->head_r_w0, hp + 256 * (size_t)D * s, st)) return fail(2);
-        if (hipMemcpyAsync(d->head_b0, w->head_b0, 256 * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-        if (hipMemcpyAsync(d->head_b0 + 256, w->head_r_b0, 256 * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-        d->head_w1 = copy_f32(w->head_w1, 3 * 256); d->head_b1 = copy_f32(w->head_b1, 3);
-        d->head_r_w1 = copy_f32(w->head_r_w1, 3 * 256); d->head_r_b1 = copy_f32(w->head_r_b1, 3);
-    } else if (rotv) {
-        // final_mlp.0 | final_mlp_rot.0 as one [64, D] product (the 3D variant's mlp_t.0 | mlp_r.0 above); hw0 also feeds the mlp.2 fold below
-        hw0 = (float *)alloc(64 * (size_t)D * 4);
-        d->head_b0 = (float *)alloc(64 * 4);
-        if (!hw0 || !d->head_b0) return fail(2);
-        if (hipMemcpyAsync(hw0, w->head_w0, 32 * (size_t)D * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-        if (hipMemcpyAsync(hw0 + 32 * (size_t)D, w->head_r_w0, 32 * (size_t)D * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-        if (hipMemcpyAsync(d->head_b0, w->head_b0, 32 * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-        if (hipMemcpyAsync(d->head_b0 + 32, w->head_r_b0, 32 * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-        d->head_w0 = pack(hw0, 64 * (size_t)D);
-        d->head_w1 = copy_f32(w->head_w1, (size_t)w->c_out * 32); d->head_b1 = copy_f32(w->head_b1, w->c_out);
-        d->head_r_w1 = copy_f32(w->head_r_w1, 4 * 32); d->head_r_b1 = copy_f32(w->head_r_b1, 4);
-    } else {
-        d->head_w0 = pack(w->head_w0, 32 * (size_t)D); d->head_b0 = copy_f32(w->head_b0, 32);
-        d->head_w1 = copy_f32(w->head_w1, (size_t)w->c_out * 32); d->head_b1 = copy_f32(w->head_b1, w->c_out);
-    }
-    if (rc) return fail(rc);
-    {
-        const bool off = (cfg().disable_folds & DA_FOLD_MLP2) != 0;
-        // (the discrete variant shares the body between the embedding and final_mlp.0, so it takes both folds; its K-wide head is the tail
-        //  kernel of da_d3pm.hip, which forms GELU(pre + sum_h pz_h) itself -- k_head_fold / k_tail_fused write at most 8 pose channels)
-        if (!off && !mfma_disabled() && (d->variant == DA_VARIANT_2D || discrete) && d->hidden % 32 == 0 && d->arch != DA_ARCH_GCN) {
-            // compose in fp32 from the caller's fp32 weights, then pack
-            const int hid = d->hidden, hc0 = d->conv[0].hc;
-            float *w2t = (float *)alloc((size_t)hid * D * 4);                  // W2^T [hidden, D]
-            float *cw = (float *)alloc((size_t)4 * hc0 * hid * 4);             // Wcat0 . W2
-            const int hwn = rotv ? 64 : 32;                                     // rows of the (stacked) first head layer
-            const float *hsrc = rotv ? hw0 : w->head_w0;
-            float *hw = (float *)alloc((size_t)hwn * hid * 4);                 // Wf0 . W2
-            d->conv0c_b = (float *)alloc((size_t)4 * hc0 * 4);
-            d->headc_b = (float *)alloc(hwn * 4);
-            if (!w2t || !cw || !hw || !d->conv0c_b || !d->headc_b) return fail(2);
-            if (launch_transpose_f32(D, hid, w->mlp_w1, w2t, st)) return fail(2);
-            const float *ws[4] = {w->conv_wq[0], w->conv_wk[0], w->conv_wv[0], w->conv_ws[0]};
-            const float *bs[4] = {w->conv_bq[0], w->conv_bk[0], w->conv_bv[0], w->conv_bs[0]};
-            for (int k = 0; k < 4; ++k) {
-                // rows of block k: [hc0, D] . W2 [D, hid]  ==  A [hc0, D] @ (W2^T [hid, D])^T
-                if (launch_gemm_simple(DA_PREC_F32, hc0, D, hid, ws[k], D, w2t, nullptr, DA_ACT_NONE, nullptr,
-                                       cw + (size_t)k * hc0 * hid, hid, st)) return fail(2);
-                // bias: b2 [1, D] @ (W_k [hc0, D])^T + b_k
-                if (launch_gemm_simple(DA_PREC_F32, 1, D, hc0, w->mlp_b1, D, ws[k], bs[k], DA_ACT_NONE, nullptr,
-                                       d->conv0c_b + (size_t)k * hc0, hc0, st)) return fail(2);
-            }
-            if (launch_gemm_simple(DA_PREC_F32, hwn, D, hid, hsrc, D, w2t, nullptr, DA_ACT_NONE, nullptr, hw, hid, st)) return fail(2);
-            if (launch_gemm_simple(DA_PREC_F32, 1, D, hwn, w->mlp_b1, D, hsrc, nullptr, DA_ACT_NONE, nullptr, d->headc_b, hwn, st)) return fail(2);
-            d->conv0c_w = pack(cw, (size_t)4 * hc0 * hid);
-            d->headc_w = pack(hw, (size_t)hwn * hid);
-            d->conv0c_wd = d->conv0c_w; d->conv0c_bd = d->conv0c_b;
-            if (d->q_prescaled) {          // dense-path variant: Q rows scaled in fp32, then packed (cw is not used afterwards)
-                d->conv0c_bd = (float *)alloc((size_t)4 * hc0 * 4);
-                if (!d->conv0c_bd) return fail(2);
-                if (hipMemcpyAsync(d->conv0c_bd, d->conv0c_b, (size_t)4 * hc0 * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-                if (scale_block(d->conv0c_bd, 1, hc0, hc0, q_scale_log2(d->conv[0].C), st)) return fail(2);
-                if (scale_block(cw, hc0, hid, hid, q_scale_log2(d->conv[0].C), st)) return fail(2);
-                d->conv0c_wd = pack(cw, (size_t)4 * hc0 * hid);
-            }
-            d->conv0c_wdp = pack_panel(d->conv0c_wd, hid, 4 * hc0);
-            if (d->n_layers > 1) d->conv0c_wqs = pack_qs(d->conv0c_wd, hid, hc0, d->conv[0].C);
-            if (d->V > 0) {            // exophormer: conv-0 projections of the virtual rows (they bypass mlp)
-                float *vq = (float *)alloc((size_t)d->V * 4 * hc0 * 4);
-                if (!vq) return fail(2);
-                for (int k = 0; k < 4; ++k)
-                    if (launch_gemm_simple(DA_PREC_F32, d->V, D, hc0, w->virt_emb, D, ws[k], bs[k], DA_ACT_NONE, nullptr,
-                                           vq + (size_t)k * hc0, 4 * hc0, st)) return fail(2);
-                d->virt_qkvs = pack(vq, (size_t)d->V * 4 * hc0);
-                d->virt_qkvs_d = d->virt_qkvs;
-                if (d->q_prescaled) {
-                    if (scale_block(vq, d->V, hc0, 4 * hc0, q_scale_log2(d->conv[0].C), st)) return fail(2);
-                    d->virt_qkvs_d = pack(vq, (size_t)d->V * 4 * hc0);
-                }
-            }
-            if (rc) return fail(rc);
-            d->fused_mlp2 = true;
-            // last conv: value heads and skip folded with final_mlp.0
-            const int L = d->n_layers - 1, hcL = d->conv[L].hc, CL = d->conv[L].C, dinL = d->conv[L].din;
-            const bool off2 = (cfg().disable_folds & DA_FOLD_LAST) != 0;
-            // (the discrete rot variant does not take this fold: both folded attention kernels exist for 32 value channels only, and its
-            //  stacked head has 64 -- it runs the last layer that disable_folds = 2 selects for the position model)
-            if (!off2 && !rotv && CL == 144 && hcL == D && dinL % 32 == 0 && (d->c_out <= 8 || discrete)) {        // (k_head_fold: 8 outputs per row at most)
-                const int nf = 2 * hcL + H * 32;
-                float *lw = (float *)alloc((size_t)nf * dinL * 4);
-                float *sw = (float *)alloc((size_t)32 * dinL * 4);
-                d->convLf_b = (float *)alloc((size_t)nf * 4);
-                d->skipc_b = (float *)alloc(32 * 4);
-                float *tmpb = (float *)alloc(32 * 4);
-                if (!lw || !sw || !d->convLf_b || !d->skipc_b || !tmpb) return fail(2);
-                const size_t blk = (size_t)hcL * dinL;
-                if (hipMemcpyAsync(lw, w->conv_wq[L], blk * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-                if (hipMemcpyAsync(lw + blk, w->conv_wk[L], blk * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-                if (hipMemcpyAsync(d->convLf_b, w->conv_bq[L], (size_t)hcL * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-                if (hipMemcpyAsync(d->convLf_b + hcL, w->conv_bk[L], (size_t)hcL * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(2);
-                for (int h = 0; h < H; ++h) {
-                    // (Wf[:, hC:(h+1)C] [32, C]) . (Wv[hC:(h+1)C, :] [C, din]) and the same block of the bias
-                    if (launch_mm_nn_f32(32, dinL, CL, w->head_w0 + (size_t)h * CL, D, w->conv_wv[L] + (size_t)h * CL * dinL, dinL,
-                                         nullptr, lw + 2 * blk + (size_t)h * 32 * dinL, dinL, st)) return fail(2);
-                    if (launch_mm_nn_f32(32, 1, CL, w->head_w0 + (size_t)h * CL, D, w->conv_bv[L] + (size_t)h * CL, 1, nullptr,
-                                         d->convLf_b + 2 * hcL + h * 32, 1, st)) return fail(2);
-                }
-                // skip: Wf [32, D] . Ws [D, din];  bias: Wf . bs + bf0
-                if (launch_mm_nn_f32(32, dinL, D, w->head_w0, D, w->conv_ws[L], dinL, nullptr, sw, dinL, st)) return fail(2);
-                if (launch_mm_nn_f32(32, 1, D, w->head_w0, D, w->conv_bs[L], 1, w->head_b0, d->skipc_b, 1, st)) return fail(2);
-                if (d->q_prescaled) {          // this projection only ever feeds the matrix-core attention
-                    if (scale_block(lw, hcL, dinL, dinL, q_scale_log2(CL), st)) return fail(2);
-                    if (scale_block(d->convLf_b, 1, hcL, hcL, q_scale_log2(CL), st)) return fail(2);
-                }
-                d->convLf_w = pack(lw, (size_t)nf * dinL);
-                d->convLf_wp = pack_panel(d->convLf_w, dinL, nf);
-                d->last_qproj = attn_last_qproj_enabled() && precision == DA_PREC_BF16 && H == 8 && dinL == 256 && d->q_prescaled && d->convLf_w && !mfma_disabled();
-                if (d->last_qproj) {
-                    d->convLf_wp_kv = pack_panel((const char *)d->convLf_w + blk * s, dinL, nf - hcL);
-                    d->convLf_wq = alloc(w_qlast_bytes(H, CL, dinL));
-                    if (!d->convLf_wq || pack_w_qlast(H, CL, dinL, d->convLf_w, d->convLf_wq, st)) return fail(2);
-                }
-                d->skipc_w = pack(sw, (size_t)32 * dinL);
-                if (rc) return fail(rc);
-                d->lastfold = true;
-            }
-        }
-    }
-    if (hipStreamSynchronize(st) != hipSuccess) { set_error("da_denoiser_create: sync failed"); return fail(2); }
-    {   // side stream of the hybrid path (see the struct); da_config.disable_folds bit 32 keeps everything on one stream
-        if (d->V > 0 && !(cfg().disable_folds & DA_FOLD_HYBRID_OVERLAP)) {
-            if (hipStreamCreateWithFlags(&d->side_stream, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&d->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&d->ev_join, hipEventDisableTiming) != hipSuccess) {
-                set_error("da_denoiser_create: side stream / events");
-                return fail(2);
-            }
-        }
-    }
-    d->dense_only = d->heads == 8 && !dense_disabled() && !mfma_disabled();
-    for (int l = 0; l < d->n_layers; ++l) d->dense_only = d->dense_only && (d->conv[l].C == 32 || d->conv[l].C == 144);
-    if (d->arch == DA_ARCH_GCN) d->dense_only = true;     // complete / banded plans aggregate in closed form (da_gcn.hip): no CSR
+    const int rc = denoiser_build(d, w, (hipStream_t)stream);       // da_denoiser_create.hip
+    if (rc) { da_denoiser_destroy(d); return rc; }
     *out = d;
     return 0;
 }
@@ -1075,7 +263,7 @@ int da_denoiser_set_features(da_denoiser *d, const da_graph *g, const float *fea
     DA_REQUIRE(workspace_bytes >= w.total, "workspace too small: %zu < %zu", workspace_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
     if ((rc = launch_set_feats(d->prec, g->n_real, d->F, d->D, feats, w.comb_in, st))) return rc;
-    if (!mfma_disabled()) {       // loop-invariant part of mlp.0 (see forward_impl); unsupported shapes fall back there
+    if (!mfma_disabled()) {       // loop-invariant part of mlp.0 (see da_forward.hip: embed_mlp); unsupported shapes fall back there
         rc = launch_gemm_mfma(d->prec, g->n_real, d->F, d->hidden, w.comb_in, d->D, d->mlp_w0, d->mlp_b0, DA_ACT_NONE, nullptr,
                               w.feat_proj, d->hidden, nullptr, st, d->D, nullptr);
         if (rc > 0) return rc;
@@ -1571,7 +759,7 @@ int da_conv_dense_ex(int prec, const da_graph *g, int heads, int C, int Din, con
     qs.Q = base; qs.K = base + hb; qs.Vt = base + 2 * hb; qs.S = folded ? nullptr : base + 3 * hb;
     qs.Cv = folded ? 32 : 0;
     const int nout = folded ? 2 * (int)hc + heads * 32 : 4 * (int)hc;
-    // the layer form the sampling loop takes for hidden layers of large complete graphs (run_forward): the projection happens in the prologue of
+    // the layer form the sampling loop takes for hidden layers of large complete graphs (da_forward.hip: dense_layer): the projection happens in the prologue of
     // the resident attention kernel; its per-head weight fragments are packed into the scratch's (then unused, adjacent) K and V regions
     const bool qsf = attn_qsf_enabled() && !folded && !residual && !g->hybrid && g->n_nodes == g->n_real && b && w_qs_bytes(heads, Din) <= 2 * hb &&
                      attn_qsf_applicable(prec, heads, C, Din, g->n_graphs, g->max_graph_nodes, g->n_pad, (flags & DA_CONV_Q_PRESCALED) ? 1 : 0);

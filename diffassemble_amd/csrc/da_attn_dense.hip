@@ -922,7 +922,7 @@ int launch_attn_dense(int prec, const DenseLayout &L, int heads, int C, int n_gr
     return C == 32 ? launch_tc<float, 32>(p, st) : launch_tc<float, 144>(p, st);
 }
 
-// The conditions under which launch_attn_dense hands a hidden layer to k_attn_res<.., 64> (da_api.hip asks INSTEAD of launching the layer's
+// The conditions under which launch_attn_dense hands a hidden layer to k_attn_res<.., 64> (da_forward.hip: layer_qsf asks INSTEAD of launching the layer's
 // projection kernel).  launch_attn_dense refuses (DA_REQUIRE) a layout with x set that does not end up there.
 bool attn_res_qsf_shape_ok(int max_nodes, int n_pad, int n_graphs, int kin);          // da_attn_opt.hip
 bool attn_qsf_applicable(int prec, int heads, int C, int kin, int n_graphs, int max_graph_nodes, int n_pad, int q_prescaled) {

@@ -236,9 +236,9 @@ __global__ __launch_bounds__(512) void k_gemm_xpanel(GemmParams p, const u32x4 *
 // Round 5, last session: re-judged under the two-graph pair loop (profiles/r05/r05_xpanel_under_split_graphs.log): -0.45 % alone (six pairs of
 // seven) and, together with the tail kernel's next-step embedding (DA_TAIL_NEXT), -2.5 % on the headline step (seven of seven) -- configuration 2
 // (144-piece graphs) does not gain.  DA_ENABLE_XPANEL: 1 = every Batch, 0 = never, unset = DA_STEP_AUTO's rule (xpanel_mode() == 2: Batches
-// whose largest graph has >= 512 pieces, decided per forward in da_api.hip).
+// whose largest graph has >= 512 pieces, decided per forward in da_forward.hip: dense_layer).
 // da_config.xpanel (DA_ENABLE_XPANEL): 1 = every Batch, 0 = never, -1 (default) = Batches whose largest graph has >= 512 pieces, decided per
-// forward in da_api.hip (xpanel_mode() == 2).  In an EXPERIMENTS build a process that sets one of the other projection kernels' own switches is
+// forward in da_forward.hip (xpanel_mode() == 2).  In an EXPERIMENTS build a process that sets one of the other projection kernels' own switches is
 // measuring THAT kernel: the rule stays out of its way.
 int xpanel_mode() {
     const int v = cfg().xpanel;

@@ -34,7 +34,7 @@ __device__ __forceinline__ float ddim2d_value(const DeviceSchedule &s, int mean_
 }
 
 // Sampling loop: the deterministic DDIM update (eta = 0, scalar timestep) applied by the head kernel itself --
-// one launch less per step.  `done` is set by forward_impl when the folded head took it.
+// one launch less per step.  `done` is set by forward_impl (da_forward.hip) when the folded head took it.
 struct DdimFuse {
     DeviceSchedule s;
     int mean_type, ratio, prev_all_nonneg;
@@ -150,7 +150,7 @@ struct QkvScatter {            // where the fused projection scatters its four c
 struct DenseLayout {
     const void *Q, *K, *Vt, *S;
     int n_pad;
-    int q_prescaled = 0;       // Q rows already carry log2(e) / sqrt(C) (projection weights scaled at pack time, da_api.hip ConvW::wd)
+    int q_prescaled = 0;       // Q rows already carry log2(e) / sqrt(C) (projection weights scaled at pack time, da_denoiser.h ConvW::wd)
     // the layer's projection inside the resident attention kernel (attn_qsf_applicable; no projection kernel runs: the attention kernel writes Q / S
     // itself and keeps K | V in LDS):
     const void *x = nullptr;   // the layer's input rows [N][ldx], bf16

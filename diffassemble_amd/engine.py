@@ -921,7 +921,7 @@ def conv_dense_ex(plan: GraphPlan, x, weight, bias, heads, C_head, residual=None
     """da_conv_dense_ex: the layer in the forms the packed denoiser runs it.  ``weight`` / ``bias`` arrive UNSCALED in fp32
     (rows Q | K | V | skip, or Q | K | V' [H * 32] when ``folded``); with ``prescale_q=True`` the Q rows are multiplied
     by log2(e) / sqrt(C) here, in fp32, before the rounding to the activation dtype -- what da_denoiser_create does
-    (da_api.hip ConvW::wd) -- and the kernels take their shift-free softmax paths (``"done"``: the caller's Q rows
+    (da_denoiser.h ConvW::wd) -- and the kernels take their shift-free softmax paths (``"done"``: the caller's Q rows
     already carry the factor; ``False``: plain da_conv_dense semantics).  Returns [N, H*C] or, folded,
     [H, n_real, 32] (per-head normalised outputs)."""
     import math

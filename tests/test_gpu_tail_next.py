@@ -89,7 +89,7 @@ torch.save(out, sys.argv[1])
 
 
 def test_step_auto_rule_selects_by_graph_size_subprocess(tmp_path):
-    """The large-graph step rule (da_config.xpanel = tail_next = -1; da_gemm_xpanel.hip xpanel_mode, da_api.hip enqueue_loop / forward_impl): with neither switch set, Batches
+    """The large-graph step rule (da_config.xpanel = tail_next = -1; da_gemm_xpanel.hip xpanel_mode, da_api.hip enqueue_loop / da_forward.hip forward_impl): with neither switch set, Batches
     whose largest graph has >= 512 pieces take the row-panel projections AND the tail kernel's next-step embedding -- bit for bit what
     DA_ENABLE_XPANEL=1 DA_TAIL_NEXT=1 gives -- and smaller graphs take neither (bit for bit both switches 0).  The 900-piece loops with and
     without the rule agree in their first step exactly and afterwards far inside bf16 resolution of the poses."""
