@@ -285,6 +285,9 @@ PROTOTYPES = {
     "da_score2d": (C.c_int, [C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
     "da_render2d_frame_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "da_render2d": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int64, _fp, _fp, C.c_int64, _fp, _fp]),
+    "da_puzzle_batch": (C.c_int, [C.c_int, C.c_int, _fp, C.c_int64, _fp, _fp, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp,
+                                  _fp, _fp, _fp]),
+    "da_complete_edges": (C.c_int, [C.c_int, _fp, C.c_int64, _fp, _fp]),
     "da_encoder_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "da_encoder_forward": (C.c_int, [C.c_int, C.POINTER(DaEncoderWeights), C.c_int, _fp, _fp, C.c_int, _fp, C.c_size_t,
                                      C.c_int, C.c_int, _fp]),

@@ -862,6 +862,33 @@ int da_render2d(int n_steps, int n_puzzles, int n_pieces, int max_tiles, const f
                 long long step_stride, const int32_t *coef, const int32_t *puzzles, long long step_bytes, uint8_t *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * A 2D Batch from whole images: every per-piece tensor in ONE launch, one workgroup per output piece, no atomics, no host
+ * sync, no allocation.  Replaces the host loops of dataset/puzzle_dataset.py: divide_images_into_patches (:175-190) and the
+ * get() of Puzzle_Dataset (:257-300), Puzzle_Dataset_Pad (zero_margin :326-332), Puzzle_Dataset_ROT_MP (:403-485),
+ * Puzzle_Dataset_MP (:507-544) and Puzzle_Dataset_ROT (:580-700) -- per piece an Image.fromarray, a .rotate(r * 90), an
+ * np.array and a / 255.  Nothing is drawn here: the turns and the kept cells arrive in `pieces`.
+ * `images`: the puzzles' pictures, uint8 HWC RGB of [32 * rows, 32 * cols, 3], image_bytes in all.  `puzzles` [n_puzzles, 8]
+ * int32: the low and high word of the picture's byte offset (a multiple of 16), rows, cols, first output piece, pieces
+ * present, and the starts of linspace(-1, 1, cols) and linspace(-1, 1, rows) inside `lin` [n_lin] fp32 (torch.linspace's own
+ * values: it is not -1 + i * step in fp32).  `pieces` [n_pieces, 4] int32 per OUTPUT piece: puzzle, source cell i * cols + j,
+ * quarter turns r in 0 .. 3, 0.  `unit` [256] fp32: uint8 / 255 as torch computes it.
+ * patches [n_pieces, views, 3, 32, 32] fp32 (views = 1 or 4): view k = the cell's crop turned counter-clockwise by
+ * (r + k) % 4 quarter turns (np.rot90 = PIL.Image.rotate(90 t) of a square tile), colour = unit[byte], then the `padding`
+ * outermost pixels (0 .. 16) of every side zeroed.  x [n_pieces, x_cols] fp32 (x_cols = 2 or 4): (x_j, y_i) and, with 4,
+ * (cos, sin) = rot as floats.  rot [n_pieces, 2] int64 = one_hot(r) @ [[1, 0], [0, 1], [-1, 0], [0, -1]]; rot_index, indexes
+ * (= the cell), batch (= the puzzle): [n_pieces] int64.  Every element of every output is written.  A table entry that
+ * points outside the buffers writes nothing for its piece.
+ * da_complete_edges: edge_index [2, n_edges] int64 of the Batch's complete graphs with self loops, in the order of
+ * dense_to_sparse(torch.ones(n, n)) per puzzle (:280-284, :472-473: source-major), shifted by the puzzle's first piece.
+ * `table` [n_puzzles, 3] int64: first edge, first piece, pieces n_g; n_edges = the sum of n_g * n_g.
+ * ------------------------------------------------------------------------------------- */
+int da_puzzle_batch(int n_puzzles, int n_pieces, const uint8_t *images, long long image_bytes, const int32_t *puzzles,
+                    const int32_t *pieces, const float *lin, int n_lin, const float *unit, int padding, int views, int x_cols,
+                    float *patches, float *x, long long *rot, long long *rot_index, long long *indexes, long long *batch,
+                    void *stream);
+int da_complete_edges(int n_puzzles, const long long *table, long long n_edges, long long *edge_index, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * 2D piece encoder: the P4 group-equivariant ResNet-18 the reference builds
  * for model='resnet18equiv', eval-mode BatchNorm.  Replaces Eff_GAT.visual_features
  * (backbones/efficient_gat.py:149-189) = normalise + ResNet.forward (backbones/resnet_equivariant.py:
