@@ -8,6 +8,8 @@ include/diffassemble_hip.h.  ``diffassemble_amd.model`` mirrors the reference's
 from . import _lib  # noqa: F401
 from .engine import DenoiserEngine, Schedule  # noqa: F401
 from .graph_plan import GraphPlan, build_plan, exophormer_edge_index  # noqa: F401
+from .fragment_batch import FragmentBatch, make_batch3d  # noqa: F401
 from .puzzle_batch import PuzzleBatch, make_batch  # noqa: F401
 
-__all__ = ["DenoiserEngine", "Schedule", "GraphPlan", "build_plan", "exophormer_edge_index", "PuzzleBatch", "make_batch"]
+__all__ = ["DenoiserEngine", "Schedule", "GraphPlan", "build_plan", "exophormer_edge_index", "PuzzleBatch", "make_batch", "FragmentBatch",
+           "make_batch3d"]

@@ -889,6 +889,34 @@ int da_puzzle_batch(int n_puzzles, int n_pieces, const uint8_t *images, long lon
 int da_complete_edges(int n_puzzles, const long long *table, long long n_edges, long long *edge_index, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * A 3D Batch from fragment meshes: the surface samples, the centring, the turn, the shuffle and the fp32 layout of every part in
+ * two launches, no atomics, no host sync, no allocation.  Replaces the per-part host loop of dataset/breakingbad_dt.py
+ * (:113-149: trimesh.sample.sample_surface, _recenter_pc, _rotate_pc, _shuffle_pc, _pad_data) in fp64 numpy.  Nothing is drawn
+ * here: the picks, the barycentric pairs, the turns and the point order are arguments.  All arithmetic is fp64, unfused.
+ * The meshes: `vertices` [n_vertices, 3] fp64, `faces` [n_faces, 3] int32 with indices LOCAL to the part, `vert_ptr` / `face_ptr`
+ * [n_parts + 1] int64: part s owns the rows vert_ptr[s] .. vert_ptr[s + 1] - 1 (at least one of each).  A face index outside
+ * the part is clamped into it; a part whose rows lie outside the buffers is skipped (nothing is written for it).
+ * da_mesh_cum_area: cum [n_faces] fp64, per part the inclusive running sum of 0.5 * |(v1 - v0) x (v2 - v0)|, summed in chunks
+ * of 256 faces with a carry, in an order that depends on the face count alone (the same bits on every run; not the bits of a
+ * sequential sum).
+ * da_fragment_batch: one workgroup per OUTPUT part k; `parts` [n_out, 2] int32 = (input part s, object).  The draws are indexed
+ * by the INPUT part: u_face [n_parts, n_points] fp64, u_len [n_parts, n_points, 2] fp64, rot [n_parts, 9] fp64 (row-major),
+ * perm [n_parts, n_points] int32 (a gather index list, clamped to 0 .. n_points - 1).
+ * Point i: pick = u_face[i] * cum[last], face = the first with cum >= pick (NaN ordered last, as numpy.searchsorted does: a
+ * non-finite vertex makes the part's points NaN as on the host), clamped to the last; (a, b) = u_len[i], replaced
+ * by (|a - 1|, |b - 1|) when a + b > 1; point = (a (v1 - v0) + b (v2 - v0)) + v0.  centroid = (sum of the points, in a fixed
+ * order) / n_points.  pcds [n_out, n_points, 3] fp32: row j = fp32(rot @ (point[perm[j]] - centroid)).  x [n_out, 7] fp32 =
+ * fp32 of the scalar-first quaternion of rot^T (scipy's from_matrix branch choice and sign), fp32(centroid).  batch [n_out] int64 = the object.  face_index [n_out, n_points] int32 or NULL: the face of point i.
+ * n_points is 1 .. 2048: the points wait in LDS as fp64, 24 bytes each, beside 6 KiB of reduction scratch.
+ * ------------------------------------------------------------------------------------- */
+int da_mesh_cum_area(int n_parts, const double *vertices, long long n_vertices, const int32_t *faces, long long n_faces,
+                     const long long *vert_ptr, const long long *face_ptr, double *cum, void *stream);
+int da_fragment_batch(int n_out, int n_parts, int n_points, const double *vertices, long long n_vertices, const int32_t *faces,
+                      long long n_faces, const long long *vert_ptr, const long long *face_ptr, const double *cum,
+                      const int32_t *parts, const double *u_face, const double *u_len, const double *rot,
+                      const int32_t *perm, float *pcds, float *x, long long *batch, int32_t *face_index, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * 2D piece encoder: the P4 group-equivariant ResNet-18 the reference builds
  * for model='resnet18equiv', eval-mode BatchNorm.  Replaces Eff_GAT.visual_features
  * (backbones/efficient_gat.py:149-189) = normalise + ResNet.forward (backbones/resnet_equivariant.py:
