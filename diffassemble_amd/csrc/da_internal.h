@@ -77,7 +77,8 @@ int launch_ddim2d(const DeviceSchedule &s, int mean_type, int n, int c, const fl
 int launch_ddpm2d(const DeviceSchedule &s, int n, int c, const float *x, const float *mo, const int64_t *t,
                   int64_t t_scalar, const float *noise, float *x_prev, hipStream_t st);
 int launch_convert(int prec, size_t n, const float *src, void *dst, hipStream_t st);
-int launch_transpose_f32(int rows, int cols, const float *src, float *dst, hipStream_t st);      // da_train.hip
+// da_train_gemm.hip: the products and sums of the training paths that more than one subsystem calls (the denoiser's own record: da_train.h)
+int launch_transpose_f32(int rows, int cols, const float *src, float *dst, hipStream_t st);      // dst[c][r] = src[r][c]
 // C (+)= A^T B over rows (A [M, N], B [M, K] row-major; split-row partials through `partial`, >= 16 M floats)
 int launch_gemm_tn(int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc, float *partial,
                    hipStream_t st, bool bfc = false);      // bfc: operands rounded to bf16 inside the kernel (DA_TRAIN_MMA_BF16)

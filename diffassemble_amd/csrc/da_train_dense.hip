@@ -24,7 +24,7 @@
 #include <mutex>
 #include <vector>
 
-#include "da_gemm_common.h"
+#include "da_train.h"
 
 namespace da {
 
@@ -832,7 +832,7 @@ __global__ __launch_bounds__(256) void k_pair_rows(int mode, int n_nodes, int H,
                                                    const int32_t *__restrict__ node_graph, const long long *__restrict__ poff,
                                                    float *P, float *dP) {
     const int lane = threadIdx.x & 63;
-    // grid-stride over the (node, head) rows: the launch caps the grid (gridsz), a Batch has more rows than that cap
+    // grid-stride over the (node, head) rows: the launch caps the grid (grid_for), a Batch has more rows than that cap
     // covers from 4 097 nodes on (the first version returned for them and left raw scores in P)
     const long long n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
     for (long long wv = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; wv < (long long)n_nodes * H; wv += n_waves) {
@@ -887,8 +887,6 @@ __global__ __launch_bounds__(256) void k_node_graph(int G, const int32_t *__rest
     if (g >= G) return;
     for (int i = gp[g] + threadIdx.x; i < gp[g + 1]; i += blockDim.x) node_graph[i] = g;
 }
-
-static unsigned gridsz(size_t n) { const size_t b = (n + 255) / 256; return (unsigned)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
 
 // the one-workgroup-per-group kernel takes a product (bf16-operand mode, every dimension <= 160; DA_GGEMM_SMALL=0: never)
 static bool ggemm_small_ok(const GGemm &p, int maxn) {
@@ -952,8 +950,8 @@ int dense_train_attn_fwd(const da_graph *g, int H, int C, const float *qkvs, con
     const bool fused_rows = ggemm_small_ok(s, mx);       // small groups: the row softmax runs in the product's epilogue
     if (fused_rows) { s.epi = 1; s.nodiag = g->dense == 2; s.pair_bf16 = 1; }
     if ((rc = ggemm(s, G, H, mx, st))) return rc;
-    if (!fused_rows) k_pair_rows<<<gridsz((size_t)n * H * 64), 256, 0, st>>>(0, n, H, g->dense == 2, g->graph_ptr, node_graph, poff, P, nullptr);
-    k_init_out<<<gridsz((size_t)n * HC), 256, 0, st>>>(n, HC, qkvs, res, o);
+    if (!fused_rows) k_pair_rows<<<grid_for((size_t)n * H * 64), 256, 0, st>>>(0, n, H, g->dense == 2, g->graph_ptr, node_graph, poff, P, nullptr);
+    k_init_out<<<grid_for((size_t)n * HC), 256, 0, st>>>(n, HC, qkvs, res, o);
     DA_LAUNCH_CHECK();
     GGemm pv;
     pv.bfc = bfc;
@@ -994,7 +992,7 @@ int dense_train_attn_bwd(const da_graph *g, int H, int C, const float *qkvs, con
     if (fused_rows) { q.epi = 2; q.E = P; }
     if ((rc = ggemm(q, G, H, mx, st))) return rc;
     q.epi = 0; q.E = nullptr;
-    if (!fused_rows) k_pair_rows<<<gridsz((size_t)n * H * 64), 256, 0, st>>>(1, n, H, 0, g->graph_ptr, node_graph, poff, (float *)P, dP);
+    if (!fused_rows) k_pair_rows<<<grid_for((size_t)n * H * 64), 256, 0, st>>>(1, n, H, 0, g->graph_ptr, node_graph, poff, (float *)P, dP);
     DA_LAUNCH_CHECK();
     // dQ = scale dS K
     q.A = {dP, 1, 0, 0}; q.B = {(float *)qkvs + HC, 0, 4 * HC, C}; q.C = {dY4, 0, 4 * HC, C};
@@ -1004,7 +1002,7 @@ int dense_train_attn_bwd(const da_graph *g, int H, int C, const float *qkvs, con
     q.A = {dP, 1, 0, 0}; q.B = {(float *)qkvs, 0, 4 * HC, C}; q.C = {dY4 + HC, 0, 4 * HC, C};
     q.transA = 1; q.transB = 0; q.dimM = 0; q.dimN = C; q.dimK = 0; q.alpha = scale;
     if ((rc = ggemm(q, G, H, mx, st))) return rc;
-    k_copy_skip_grad<<<gridsz((size_t)n * HC), 256, 0, st>>>(n, HC, d_o, dY4);
+    k_copy_skip_grad<<<grid_for((size_t)n * HC), 256, 0, st>>>(n, HC, d_o, dY4);
     DA_LAUNCH_CHECK();
     return 0;
 }
@@ -1018,7 +1016,7 @@ int dense_train_attn_bwd(const da_graph *g, int H, int C, const float *qkvs, con
 // by destination (irr_row_ptr / irr_col_src) + by source (out_ptr / out_dst of a hybrid training graph).  ONE softmax per
 // (target, head) spans both parts: statistics (max, 1 / (sum + 1e-16)) are computed over the masked dense row AND the row's
 // remainder edges, the dense part of P is kept, the remainder weights are recomputed from the statistics wherever needed --
-// exactly what the CSR kernels of da_train.hip do for whole graphs.
+// exactly what the CSR kernels of da_train_attn.hip do for whole graphs.
 // rows of the pair matrices + their remainder edges: one wave per (node, head); virtual rows (node >= n_real) have no dense part.
 //   mode 0: S (scaled scores) -> P in place (masked entries 0), stats[node, h] = (max, 1 / (sum + 1e-16)) over both parts
 //   mode 2: Dd[node, h] = sum_j P_ij dP_ij over the dense part (virtual rows: 0)
@@ -1145,7 +1143,7 @@ template <int EPL> struct IrrU { static constexpr int v = EPL <= 4 ? 4 : 2; };  
 template <int EPL> struct IrrNW { static constexpr int v = EPL <= 4 ? 16 : 8; };      // (eight at C = 144: the pipelined loop wants more than the 128 registers of a 1024-thread block)     // waves of a heavy row's workgroup (LDS: v x 64 x (EPL + 1) floats)
 
 // o[i, :] += sum over i's remainder edges of p_e v_src, p_e = exp(s_e - m_i) inv_i from the combined statistics.  Wave per
-// destination, lane = EPL contiguous channels of the H*C-wide rows (8 lanes per head), as the CSR kernels of da_train.hip.
+// destination, lane = EPL contiguous channels of the H*C-wide rows (8 lanes per head), as the CSR kernels of da_train_attn.hip.
 template <int EPL, bool HEAVY>
 __global__ __launch_bounds__(HEAVY ? 64 * IrrNW<EPL>::v : 256) void k_attn_irr_fwd(int n_nodes, int n_real, const int32_t *__restrict__ irr_ptr, const int32_t *__restrict__ irr_src,
                                                       int H, int HC, const float *__restrict__ qkvs, const float *__restrict__ stats,
@@ -1912,10 +1910,10 @@ int hybrid_train_attn_fwd(const da_graph *g, int H, int C, const float *qkvs, co
         auto virtual_chain = [&]() -> int {
             // virtual rows: statistics over their (remainder-only) edges, o = skip (+ residual), then their edges -- rows with more
             // than IRR_HEAVY edges by workgroups, the others (the virtual nodes of small puzzles) by waves
-            k_pair_rows_hybrid<<<gridsz((size_t)(n - nr) * H * 64), 256, 0, sv>>>(0, nr, n, nr, H, C, g->graph_ptr, g->pad_ptr, node_graph, poff, g->mask,
+            k_pair_rows_hybrid<<<grid_for((size_t)(n - nr) * H * 64), 256, 0, sv>>>(0, nr, n, nr, H, C, g->graph_ptr, g->pad_ptr, node_graph, poff, g->mask,
                                                                                (const long long *)g->mask_ptr, g->irr_row_ptr, g->irr_col_src, qkvs, nullptr,
                                                                                nullptr, stats, nullptr);
-            k_init_out<<<gridsz((size_t)(n - nr) * HC), 256, 0, sv>>>(n - nr, HC, qkvs + (size_t)nr * 4 * HC, res ? res + (size_t)nr * HC : nullptr, o + (size_t)nr * HC);
+            k_init_out<<<grid_for((size_t)(n - nr) * HC), 256, 0, sv>>>(n - nr, HC, qkvs + (size_t)nr * 4 * HC, res ? res + (size_t)nr * HC : nullptr, o + (size_t)nr * HC);
             const int grid_v = (int)(((size_t)(n - nr) * 64 + 255) / 256);
             DA_HYB_SWITCH(C, (k_attn_irr_fwd<4, false><<<grid_v, 256, 0, sv>>>(n, nr, g->irr_row_ptr, g->irr_col_src, H, HC, qkvs, stats, o, scale_f, nr)),
                           (k_attn_irr_fwd<18, false><<<grid_v, 256, 0, sv>>>(n, nr, g->irr_row_ptr, g->irr_col_src, H, HC, qkvs, stats, o, scale_f, nr)))
@@ -1945,10 +1943,10 @@ int hybrid_train_attn_fwd(const da_graph *g, int H, int C, const float *qkvs, co
     s.H = H; s.gp = g->graph_ptr; s.poff = poff;
     int rc;
     if ((rc = ggemm(s, G, H, mx, st))) return rc;
-    k_pair_rows_hybrid<<<gridsz((size_t)n * H * 64), 256, 0, st>>>(0, 0, n, nr, H, C, g->graph_ptr, g->pad_ptr, node_graph, poff, g->mask,
+    k_pair_rows_hybrid<<<grid_for((size_t)n * H * 64), 256, 0, st>>>(0, 0, n, nr, H, C, g->graph_ptr, g->pad_ptr, node_graph, poff, g->mask,
                                                                     (const long long *)g->mask_ptr, g->irr_row_ptr, g->irr_col_src, qkvs, P,
                                                                     nullptr, stats, nullptr);
-    k_init_out<<<gridsz((size_t)n * HC), 256, 0, st>>>(n, HC, qkvs, res, o);
+    k_init_out<<<grid_for((size_t)n * HC), 256, 0, st>>>(n, HC, qkvs, res, o);
     DA_LAUNCH_CHECK();
     GGemm pv;
     pv.bfc = bfc;
@@ -1995,7 +1993,7 @@ int hybrid_train_attn_bwd(const da_graph *g, int H, int C, const float *qkvs, co
         // the virtual rows' chain: dk | dv start from zero; as destinations their dq (and skip gradient), as sources the dk | dv of
         // their edges into the real rows -- none of it touches a real row's gradient
         auto virtual_chain = [&]() -> int {
-            k_zero_kv_grad<<<gridsz((size_t)(n - nr) * 2 * HC), 256, 0, sv>>>(nr, n, HC, dY4);
+            k_zero_kv_grad<<<grid_for((size_t)(n - nr) * 2 * HC), 256, 0, sv>>>(nr, n, HC, dY4);
             DA_HYB_SWITCH(C, (k_attn_irr_bwd_dst<4, false><<<grid_v, 256, 0, sv>>>(n, nr, g->irr_row_ptr, g->irr_col_src, H, HC, qkvs, d_o, stats, dY4, Dd, scale, DTOT, nr)),
                           (k_attn_irr_bwd_dst<18, false><<<grid_v, 256, 0, sv>>>(n, nr, g->irr_row_ptr, g->irr_col_src, H, HC, qkvs, d_o, stats, dY4, Dd, scale, DTOT, nr)))
             DA_HYB_SWITCH(C, (k_attn_irr_bwd_dst<4, true><<<n - nr, 64 * IrrNW<4>::v, 0, sv>>>(n, nr, g->irr_row_ptr, g->irr_col_src, H, HC, qkvs, d_o, stats, dY4, Dd, scale, DTOT, 0)),
@@ -2031,12 +2029,12 @@ int hybrid_train_attn_bwd(const da_graph *g, int H, int C, const float *qkvs, co
     q.A = {(float *)P, 1, 0, 0}; q.B = {(float *)d_o, 0, HC, C}; q.C = {dY4 + 2 * HC, 0, 4 * HC, C};
     q.transA = 1; q.transB = 0; q.dimM = 0; q.dimN = C; q.dimK = 0; q.alpha = 1.0f;
     if ((rc = ggemm(q, G, H, mx, st))) return rc;
-    if (n > nr) { k_zero_kv_grad<<<gridsz((size_t)(n - nr) * 2 * HC), 256, 0, st>>>(nr, n, HC, dY4); DA_LAUNCH_CHECK(); }
+    if (n > nr) { k_zero_kv_grad<<<grid_for((size_t)(n - nr) * 2 * HC), 256, 0, st>>>(nr, n, HC, dY4); DA_LAUNCH_CHECK(); }
     // dP = dO V^T ; D (dense part)
     q.A = {(float *)d_o, 0, HC, C}; q.B = {(float *)qkvs + 2 * HC, 0, 4 * HC, C}; q.C = {dP, 1, 0, 0};
     q.transA = 0; q.transB = 1; q.dimM = 0; q.dimN = 0; q.dimK = C; q.alpha = 1.0f;
     if ((rc = ggemm(q, G, H, mx, st))) return rc;
-    k_pair_rows_hybrid<<<gridsz((size_t)n * H * 64), 256, 0, st>>>(2, 0, n, nr, H, C, g->graph_ptr, g->pad_ptr, node_graph, poff, g->mask,
+    k_pair_rows_hybrid<<<grid_for((size_t)n * H * 64), 256, 0, st>>>(2, 0, n, nr, H, C, g->graph_ptr, g->pad_ptr, node_graph, poff, g->mask,
                                                                     (const long long *)g->mask_ptr, g->irr_row_ptr, g->irr_col_src, qkvs,
                                                                     (float *)P, dP, nullptr, Dd);
     // remainder, destination side: D total, dq of the remainder edges, skip gradient
@@ -2045,7 +2043,7 @@ int hybrid_train_attn_bwd(const da_graph *g, int H, int C, const float *qkvs, co
     if (n > nr) DA_HYB_SWITCH(C, (k_attn_irr_bwd_dst<4, true><<<n - nr, 64 * IrrNW<4>::v, 0, st>>>(n, nr, g->irr_row_ptr, g->irr_col_src, H, HC, qkvs, d_o, stats, dY4, Dd, scale, DTOT, 0)),
                   (k_attn_irr_bwd_dst<18, true><<<n - nr, 64 * IrrNW<18>::v, 0, st>>>(n, nr, g->irr_row_ptr, g->irr_col_src, H, HC, qkvs, d_o, stats, dY4, Dd, scale, DTOT, 0)))
     // dS = P o (dP - D) over the regular edges
-    k_pair_rows_hybrid<<<gridsz((size_t)n * H * 64), 256, 0, st>>>(1, 0, n, nr, H, C, g->graph_ptr, g->pad_ptr, node_graph, poff, g->mask,
+    k_pair_rows_hybrid<<<grid_for((size_t)n * H * 64), 256, 0, st>>>(1, 0, n, nr, H, C, g->graph_ptr, g->pad_ptr, node_graph, poff, g->mask,
                                                                     (const long long *)g->mask_ptr, g->irr_row_ptr, g->irr_col_src, qkvs,
                                                                     (float *)P, dP, nullptr, Dd);
     DA_LAUNCH_CHECK();

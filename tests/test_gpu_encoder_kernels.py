@@ -387,7 +387,7 @@ PART_CAP = 16 << 20
 
 
 def tn_splits(kind, M, N, K):
-    """the row-split count of launch_gemm_tn / launch_gemm_tn_bf16 (da_train.hip) and what set it"""
+    """the row-split count of launch_gemm_tn / launch_gemm_tn_bf16 (da_train_gemm.hip) and what set it"""
     tile, rows, chunk = (64, 256, 16) if kind == "f32" else (128, 512, 32)
     cands = {"tiles": 2048 // (-(-N // tile) * -(-K // tile)), "rows": -(-M // rows), "cap": PART_CAP // (N * K)}
     regime = min(cands, key=lambda r: (cands[r], r))
