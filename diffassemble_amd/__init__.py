@@ -10,6 +10,7 @@ from .engine import DenoiserEngine, Schedule  # noqa: F401
 from .graph_plan import GraphPlan, build_plan, exophormer_edge_index  # noqa: F401
 from .fragment_batch import FragmentBatch, make_batch3d  # noqa: F401
 from .puzzle_batch import PuzzleBatch, make_batch  # noqa: F401
+from .resize2d import make_batch_from_pictures, resize_images  # noqa: F401
 
 __all__ = ["DenoiserEngine", "Schedule", "GraphPlan", "build_plan", "exophormer_edge_index", "PuzzleBatch", "make_batch", "FragmentBatch",
-           "make_batch3d"]
+           "make_batch3d", "resize_images", "make_batch_from_pictures"]

@@ -288,6 +288,10 @@ PROTOTYPES = {
     "da_puzzle_batch": (C.c_int, [C.c_int, C.c_int, _fp, C.c_int64, _fp, _fp, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp,
                                   _fp, _fp, _fp]),
     "da_complete_edges": (C.c_int, [C.c_int, _fp, C.c_int64, _fp, _fp]),
+    "da_resize2d_window_rows": (C.c_int, []),
+    "da_resize2d_workspace_bytes": (C.c_size_t, [C.c_int, _fp]),
+    "da_resize2d": (C.c_int, [C.c_int, _fp, C.c_int64, _fp, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_size_t, C.c_int, C.c_int64, C.c_int64,
+                              C.c_int64, _fp]),
     "da_mesh_cum_area": (C.c_int, [C.c_int, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp, _fp]),
     "da_fragment_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
                                     _fp, _fp, _fp]),

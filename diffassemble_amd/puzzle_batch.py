@@ -28,8 +28,9 @@ Differences from the reference, on purpose:
 * ``rot`` (all ``(1, 0)``) and ``rot_index`` (all 0) exist without ``rotation`` too, and ``indexes`` exists in every mode;
 * the random draws are made here on the host with torch under ``generator`` (per puzzle: the turns, then the kept cells), or
   handed in; the reference draws the kept cells with Python's ``random.shuffle``;
-* the PIL resize, the augmentations, the ``random=True`` shuffle and the Exphander graphs stay with the caller
-  (``edges=None`` leaves ``edge_index`` unset).
+* the ``random=True`` shuffle and the Exphander graphs stay with the caller (``edges=None`` leaves ``edge_index`` unset); the
+  PIL resize and the flip / crop augmentations are ``resize2d.make_batch_from_pictures``, which resizes on the device and then
+  calls ``make_batch`` (the flip coin and the crop box are drawn by the caller).
 
 ``make_batch`` on a ROCm device is two library calls (``da_puzzle_batch`` and ``da_complete_edges``,
 diffassemble_amd/csrc/da_puzzle_batch.hip) after ONE upload of the small tables and one of the pictures when they
@@ -67,18 +68,18 @@ class PuzzleBatch:
         return f"PuzzleBatch({body})"
 
 
-def _image(img, g):
-    """One picture as a uint8 [H, W, 3] tensor (on whatever device it lies)."""
+def _image(img, g, who="make_batch"):
+    """One picture as a uint8 [H, W, 3] tensor (on whatever device it lies); ``who`` names the caller in the errors."""
     if not torch.is_tensor(img):
         if hasattr(img, "mode") and hasattr(img, "size") and not isinstance(img, np.ndarray):          # a PIL image
             if img.mode != "RGB":
-                raise ValueError(f"make_batch: image {g} is a PIL image of mode {img.mode!r}; convert it to 'RGB'")
+                raise ValueError(f"{who}: image {g} is a PIL image of mode {img.mode!r}; convert it to 'RGB'")
         arr = np.array(img)                         # a copy: PIL hands out read-only memory
         if arr.dtype != np.uint8:
-            raise ValueError(f"make_batch: image {g} is uint8 [H, W, 3] (got dtype {arr.dtype})")
+            raise ValueError(f"{who}: image {g} is uint8 [H, W, 3] (got dtype {arr.dtype})")
         img = torch.from_numpy(np.ascontiguousarray(arr))
     if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
-        raise ValueError(f"make_batch: image {g} is uint8 [H, W, 3] (got {img.dtype} {tuple(img.shape)})")
+        raise ValueError(f"{who}: image {g} is uint8 [H, W, 3] (got {img.dtype} {tuple(img.shape)})")
     return img
 
 
@@ -267,7 +268,7 @@ def make_batch(images, patch_per_dim, *, rotation=False, all_equivariant=False, 
     """The Batch of G puzzles cut from G pictures (see the module docstring for the rule and the differences from the reference).
 
     ``images``: a list of G uint8 ``[32 * rows_g, 32 * cols_g, 3]`` arrays, tensors or PIL RGB images, or one ``[G, H, W, 3]``
-    tensor, already resized (the resize and the augmentations stay with the caller).  ``patch_per_dim``: one ``(rows, cols)``
+    tensor, already resized (``make_batch_from_pictures`` resizes first).  ``patch_per_dim``: one ``(rows, cols)``
     for all puzzles or one per puzzle.  The reference's dataset classes are the arguments: ``Puzzle_Dataset`` the defaults,
     ``Puzzle_Dataset_ROT`` ``rotation=True`` (and ``all_equivariant``), ``Puzzle_Dataset_MP`` ``missing_perc``,
     ``Puzzle_Dataset_ROT_MP`` both, ``Puzzle_Dataset_Pad`` ``padding`` (0 .. 16).

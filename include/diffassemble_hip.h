@@ -889,6 +889,38 @@ int da_puzzle_batch(int n_puzzles, int n_pieces, const uint8_t *images, long lon
 int da_complete_edges(int n_puzzles, const long long *table, long long n_edges, long long *edge_index, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Resize a Batch's pictures: PIL.Image.resize(size, resample, box) for 8-bit RGB, byte for byte, all pictures in one call, no
+ * atomics, no host sync, no allocation, no floating point.  Replaces the img.resize((32 cols, 32 rows)) at the head of every
+ * get() of dataset/puzzle_dataset.py (:266, :344, :413, :517 bicubic, :590 Lanczos) and, with `flip` and a second call with a
+ * box, the RandomHorizontalFlip / RandomCropAndResizedToOriginal of its augmentations (:155-172).  PIL's method: a horizontal,
+ * then a vertical pass, each output byte = clamp((2^21 + sum of byte * coefficient) >> 22, 0, 255) in int32 (arithmetic shift),
+ * the horizontal result stored as uint8 before the vertical pass reads it.
+ * `src` / `dst`: the packed uint8 HWC RGB pictures, src_bytes / dst_bytes in all.  `tables` [n_table] int32: per axis of a
+ * picture a bound table [out, 2] = (first source index, count) and a coefficient table [out, ksize], count <= ksize, made on
+ * the host in fp64 (resize2d.py states the rule); a pass that PIL skips is the identity table (first = the index, count 1,
+ * coefficient 2^22).  The bounds do not decrease with the output index.
+ * `pictures` [n_pictures, 24] int32: 0-1 the low and high word of the picture's byte offset in src, 2 source height, 3 source
+ * width, 4-5 byte offset in dst, 6 output height, 7 output width, 8 flip (the OUTPUT is mirrored left to right), 9-11 the
+ * horizontal tables: start of the bounds, start of the coefficients (ints into `tables`), ksize, 12-14 the same for the
+ * vertical tables, 15 first tile of the fused route, 16 tiles per tile row = ceil(width / 32) (a tile is 64 rows x 32 columns),
+ * 17 / 18 first block of the two-pass route's horizontal / vertical launch (256 pixels a block, of [20] x width and of height
+ * x width pixels), 19-20 the first source row the vertical pass reads and how many, 21-22 byte offset of the picture's
+ * horizontal result [rows [20]][width][3] in the workspace (a multiple of 16), 23 zero.
+ * route DA_RESIZE_FUSED: one launch of n_tiles workgroups; every tile's vertical window (source rows) must be at most
+ * da_resize2d_window_rows() = 256, a tile whose window is larger writes nothing.  route DA_RESIZE_TWO_PASS: two launches
+ * (n_hblocks, n_vblocks) through `workspace`; da_resize2d_workspace_bytes(n, HOST copy of `pictures`) = the sum of
+ * 3 * [20] * [7] rounded up to 16 each.  Both routes give the same bytes.  A descriptor that points outside the buffers
+ * writes nothing for its picture.
+ * ------------------------------------------------------------------------------------- */
+#define DA_RESIZE_FUSED 0
+#define DA_RESIZE_TWO_PASS 1
+int da_resize2d_window_rows(void);
+size_t da_resize2d_workspace_bytes(int n_pictures, const int32_t *pictures_host);
+int da_resize2d(int n_pictures, const uint8_t *src, long long src_bytes, const int32_t *pictures, const int32_t *tables,
+                long long n_table, uint8_t *dst, long long dst_bytes, uint8_t *workspace, size_t workspace_bytes, int route,
+                long long n_tiles, long long n_hblocks, long long n_vblocks, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * A 3D Batch from fragment meshes: the surface samples, the centring, the turn, the shuffle and the fp32 layout of every part in
  * two launches, no atomics, no host sync, no allocation.  Replaces the per-part host loop of dataset/breakingbad_dt.py
  * (:113-149: trimesh.sample.sample_surface, _recenter_pc, _rotate_pc, _shuffle_pc, _pad_data) in fp64 numpy.  Nothing is drawn
