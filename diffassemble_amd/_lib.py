@@ -277,6 +277,11 @@ PROTOTYPES = {
     "da_loss_grad": (C.c_int, [C.c_int, C.c_size_t, _fp, _fp, _fp, _fp, _fp]),
     "da_head3d_backward": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp]),
     "da_q_sample_se3": (C.c_int, [C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    # the 3D model with use_6dof (additive to ABI 19)
+    "da_head3d_backward_ex": (C.c_int, [C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
+    "da_q_sample_se3_6d": (C.c_int, [C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "da_rot6d_to_pose": (C.c_int, [C.c_int, _fp, C.c_int, _fp, _fp]),
+    "da_rot6d_to_pose_backward": (C.c_int, [C.c_int, _fp, C.c_int, _fp, _fp, _fp]),
     "da_adafactor_step": (C.c_int, [C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_size_t, C.c_int, C.c_float,
                                     C.c_float, C.c_float, C.c_float, _fp]),
     "da_adafactor_nd_step": (C.c_int, [C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t, C.c_int, C.c_size_t, C.c_size_t,

@@ -191,10 +191,13 @@ int da_denoiser_create(const da_weights *w, int precision, void *stream, da_deno
     DA_REQUIRE(w->arch != DA_ARCH_GCN || w->n_layers == 2, "gcn arch: n_layers must be 2 (backbones/gcn.py:9-14)");
     DA_REQUIRE(w->heads == 8, "heads must be 8");
     // k_embed_pos_time keeps the pose-MLP weight rows in a fixed register array (da_basic.hip); fail here, not on the first
-    // forward or inside a hipGraph capture (the reference uses c_in = 2 / 4 in 2D and 7 in 3D)
-    DA_REQUIRE(w->c_in >= 1 && w->c_in <= 8, "da_denoiser_create: c_in = %d outside [1, 8]", w->c_in);
+    // forward or inside a hipGraph capture (the reference uses c_in = 2 / 4 in 2D and 7 in 3D, 13 in 3D with use_6dof)
     DA_REQUIRE(w->variant == DA_VARIANT_2D || w->variant == DA_VARIANT_3D || w->variant == DA_VARIANT_DISCRETE || w->variant == DA_VARIANT_DISCRETE_ROT,
                "bad variant %d", w->variant);
+    if (w->variant == DA_VARIANT_3D)       // 7: quaternion wxyz | translation; 13: quaternion | translation | a1 | a2 (use_6dof), mlp_t.2 then [9, 256]
+        DA_REQUIRE(w->c_in == 7 || w->c_in == 13, "da_denoiser_create(3D): c_in = %d is neither 7 nor 13 (use_6dof)", w->c_in);
+    else
+        DA_REQUIRE(w->c_in >= 1 && w->c_in <= 8, "da_denoiser_create: c_in = %d outside [1, 8]", w->c_in);
     const bool rotv = w->variant == DA_VARIANT_DISCRETE_ROT;           // Eff_GAT_Discrete_ROT: Eff_GAT_Discrete plus final_mlp_rot
     const bool discrete = w->variant == DA_VARIANT_DISCRETE || rotv;
     if (discrete) {
@@ -305,9 +308,9 @@ int da_ddim_step(const da_schedule *s, int variant, int mean_type, int n, int c,
     DA_REQUIRE(variant != DA_VARIANT_DISCRETE_ROT, "da_ddim_step: the discrete rot variant has no pose update (da_d3pm_rot_step)");
     DA_REQUIRE(eta == 0.f || noise, "da_ddim_step: eta > 0 needs noise");
     if (variant == DA_VARIANT_3D) {
-        DA_REQUIRE(c == 7, "da_ddim_step(3D): c must be 7");
+        DA_REQUIRE(c == 7 || c == 13, "da_ddim_step(3D): c must be 7, or 13 (use_6dof), not %d", c);
         DA_REQUIRE(eta == 0.f, "da_ddim_step(3D): eta must be 0 (the reference binds DDIM only)");
-        return launch_ddim3d(to_dev(s), mean_type, n, x, model_out, t, t_scalar, inference_ratio, prev_all_nonneg,
+        return launch_ddim3d(to_dev(s), mean_type, n, c - 4, x, model_out, t, t_scalar, inference_ratio, prev_all_nonneg,
                              x_prev, (hipStream_t)stream);
     }
     return launch_ddim2d(to_dev(s), mean_type, n, c, x, model_out, t, t_scalar, inference_ratio, prev_all_nonneg, eta,
@@ -324,7 +327,7 @@ static int enqueue_loop(da_denoiser *d, const da_graph *g, const da_schedule *s,
                         int n_iters, const float *x_init, float *traj, float *x_final, const Workspace &w,
                         hipStream_t st, const da_loop_opts *o = nullptr, size_t traj_stride = 0, size_t noise_stride = 0) {
     const int nr = g->n_real;
-    const int c = d->variant == DA_VARIANT_3D ? 7 : d->c_in;
+    const int c = d->c_in;          // (3D: 7, or 13 with use_6dof -- the pose row the model returns, da_denoiser.h: pose_width)
     const size_t bytes = (size_t)nr * c * sizeof(float);
     const DeviceSchedule ds = to_dev(s);
     const float *cur = x_init;
@@ -370,7 +373,7 @@ static int enqueue_loop(da_denoiser *d, const da_graph *g, const da_schedule *s,
         const float *nz = (o && o->noise) ? o->noise + (size_t)it * (noise_stride ? noise_stride : (size_t)nr * c) : nullptr;
         rc = timed(d, DA_PROF_UPDATE, st, [&] {
             if (d->variant == DA_VARIANT_3D)
-                return launch_ddim3d(ds, mean_type, nr, cur, w.model_out, nullptr, i, ratio, nonneg, nxt, st);
+                return launch_ddim3d(ds, mean_type, nr, t_channels(d), cur, w.model_out, nullptr, i, ratio, nonneg, nxt, st);
             if (ddpm)       // t_index == 0 adds no noise (spatial_diffusion.py:504-506)
                 return launch_ddpm2d(ds, nr, c, cur, w.model_out, nullptr, i, i == 0 ? nullptr : nz, nxt, st);
             return launch_ddim2d(ds, mean_type, nr, c, cur, w.model_out, nullptr, i, ratio, nonneg, eta, eta > 0.f ? nz : nullptr, nxt, st);
@@ -442,7 +445,7 @@ int da_sample_loop_pair_ex(da_denoiser *d, const da_schedule *s, int mean_type, 
     DA_REQUIRE((!g_a->hybrid && !g_b->hybrid) || da::cfg().pair_split, "da_sample_loop_pair: hybrid graphs need the two-graph form (da_config.pair_split = 1)");
     DA_REQUIRE(!d->prof_on, "da_sample_loop_pair: not available while profiling (event bracketing is not capturable)");
     DA_REQUIRE((traj_a == nullptr) == (traj_b == nullptr), "da_sample_loop_pair_traj: both trajectory pointers or none");
-    DA_REQUIRE(!traj_a || traj_stride >= (size_t)(g_a->n_real + g_b->n_real) * (d->variant == DA_VARIANT_3D ? 7 : d->c_in),
+    DA_REQUIRE(!traj_a || traj_stride >= (size_t)(g_a->n_real + g_b->n_real) * d->c_in,
                "da_sample_loop_pair_traj: traj_stride smaller than one iteration of both halves");
     if ((rc = check_graph(d, g_a)) || (rc = check_graph(d, g_b))) return rc;
     const Workspace wa = carve(d, g_a, workspace_a), wb = carve(d, g_b, workspace_b);

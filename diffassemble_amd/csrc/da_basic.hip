@@ -42,7 +42,9 @@ __global__ __launch_bounds__(256) void k_set_virtual_rows(int rows, int V, int D
 // lanes through a wave-private LDS row; same operation order as before.
 // Workgroups behind the embedding's own (vs.rows > 0): the exophormer's virtual rows' conv-0 projections into the head-major buffers
 // (k_scatter_virtual's job, a launch of its own on the critical path of small Batches otherwise).
-template <typename T>
+// CMAX = the length of the register array that holds a row of pos_mlp.0: 8 for every 2D model and the 7-channel 3D one, 16 for the
+// 13 pose channels of the 3D model with use_6dof (an instance of its own, so the others keep their registers).
+template <typename T, int CMAX>
 __global__ __launch_bounds__(256) void k_embed_pos_time(int n, int NPW, int c_in, int F, int D, const float *__restrict__ x,
                                                         const int64_t *__restrict__ t, int64_t t_scalar, int steps,
                                                         const float *__restrict__ time_emb,
@@ -68,12 +70,12 @@ __global__ __launch_bounds__(256) void k_embed_pos_time(int n, int NPW, int c_in
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int r0 = (blockIdx.x * 4 + wv) * NPW;
     if (r0 >= n) return;
-    float w0r[8], w1r[16];
+    float w0r[CMAX], w1r[16];
     float b0r = 0.f, b1r = 0.f;
     if (lane < 16) {
         b0r = b0[lane];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) w0r[k] = k < c_in ? w0[lane * c_in + k] : 0.f;
+        for (int k = 0; k < CMAX; ++k) w0r[k] = k < c_in ? w0[lane * c_in + k] : 0.f;
     }
     if (lane < 32) {
         b1r = b1[lane];
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(256) void k_embed_pos_time(int n, int NPW, int c_in
         if (lane < 16) {
             float a = b0r;
 #pragma unroll
-            for (int k = 0; k < 8; ++k) a += k < c_in ? w0r[k] * x[(size_t)r * c_in + k] : 0.f;
+            for (int k = 0; k < CMAX; ++k) a += k < c_in ? w0r[k] * x[(size_t)r * c_in + k] : 0.f;
             hid[wv][lane] = gelu_erf(a);
         }
         __builtin_amdgcn_wave_barrier();
@@ -245,7 +247,7 @@ int launch_embed_pos_time(int prec, int n, int c_in, int F, int D, const float *
                           int steps, const float *time_emb, const float *w0, const float *b0, const float *w1,
                           const float *b1, void *comb_in, hipStream_t st, const VirtScatter *vsp) {
     if (n <= 0) return 0;
-    if (c_in > 8) { set_error("launch_embed_pos_time: c_in %d > 8", c_in); return 2; }
+    if (c_in > 16) { set_error("launch_embed_pos_time: c_in %d > 16", c_in); return 2; }
     VirtScatter vs;
     if (vsp && vsp->rows > 0) vs = *vsp;
     const size_t vtotal = (size_t)vs.rows * 4 * vs.H * vs.C;
@@ -253,10 +255,15 @@ int launch_embed_pos_time(int prec, int n, int c_in, int F, int D, const float *
     const int npw_env = DA_XENV("DA_EMBED_NPW", 0);
     // nodes per wave: one while the batch is too small to cover the chip otherwise, eight from 8 192 nodes up
     const int npw = npw_env > 0 ? npw_env : (n >= 8192 ? 8 : 1), grid = (n + 4 * npw - 1) / (4 * npw);
-    if (prec == DA_PREC_BF16)
-        k_embed_pos_time<bf16_t><<<grid + vblocks, 256, 0, st>>>(n, npw, c_in, F, D, x, t, t_scalar, steps, time_emb, w0, b0, w1, b1, (bf16_t *)comb_in, grid, vs);
+    if (c_in > 8) {
+        if (prec == DA_PREC_BF16)
+            k_embed_pos_time<bf16_t, 16><<<grid + vblocks, 256, 0, st>>>(n, npw, c_in, F, D, x, t, t_scalar, steps, time_emb, w0, b0, w1, b1, (bf16_t *)comb_in, grid, vs);
+        else
+            k_embed_pos_time<float, 16><<<grid + vblocks, 256, 0, st>>>(n, npw, c_in, F, D, x, t, t_scalar, steps, time_emb, w0, b0, w1, b1, (float *)comb_in, grid, vs);
+    } else if (prec == DA_PREC_BF16)
+        k_embed_pos_time<bf16_t, 8><<<grid + vblocks, 256, 0, st>>>(n, npw, c_in, F, D, x, t, t_scalar, steps, time_emb, w0, b0, w1, b1, (bf16_t *)comb_in, grid, vs);
     else
-        k_embed_pos_time<float><<<grid + vblocks, 256, 0, st>>>(n, npw, c_in, F, D, x, t, t_scalar, steps, time_emb, w0, b0, w1, b1, (float *)comb_in, grid, vs);
+        k_embed_pos_time<float, 8><<<grid + vblocks, 256, 0, st>>>(n, npw, c_in, F, D, x, t, t_scalar, steps, time_emb, w0, b0, w1, b1, (float *)comb_in, grid, vs);
     DA_LAUNCH_CHECK();
     return 0;
 }

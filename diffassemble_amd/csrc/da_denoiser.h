@@ -132,6 +132,11 @@ struct Workspace {
     size_t total;
 };
 
+// Width of a pose row as the model returns it.  3D: quaternion wxyz | the translation head's outputs = c_in, 7 or (use_6dof: translation | a1 | a2)
+// 13; the translation head is t_channels = c_in - 4 wide
+inline int pose_width(const da_denoiser *d) { return d->variant == DA_VARIANT_3D ? d->c_in : d->c_out; }
+inline int t_channels(const da_denoiser *d) { return d->c_in - 4; }
+
 inline Workspace carve(const da_denoiser *d, const da_graph *g, void *base) {
     const size_t s = esize(d->prec);
     const size_t n = (size_t)g->n_nodes, nr = (size_t)g->n_real;
@@ -180,11 +185,12 @@ inline Workspace carve(const da_denoiser *d, const da_graph *g, void *base) {
         if (g->hybrid && n > nr) w.virt_part = (float *)take((n - nr) * (size_t)DA_VIRT_SPLIT_MAX * 64 * 6 * sizeof(float));
         w.dskip = take(np * (size_t)hcmax * s);
     }
-    const int cpose = d->variant == DA_VARIANT_3D ? 7 : d->c_out;
+    const int cpose = pose_width(d);
+    const size_t cbuf = cpose > 8 ? cpose : 8;
     w.model_out = (float *)take(nr * cpose * sizeof(float));
     w.model_out_unc = (float *)take(nr * cpose * sizeof(float));
-    w.xbuf0 = (float *)take(nr * 8 * sizeof(float));
-    w.xbuf1 = (float *)take(nr * 8 * sizeof(float));
+    w.xbuf0 = (float *)take(nr * cbuf * sizeof(float));
+    w.xbuf1 = (float *)take(nr * cbuf * sizeof(float));
     w.gcn_dinv = d->arch == DA_ARCH_GCN ? (float *)take(n * sizeof(float)) : nullptr;
     w.proj4_stride = align_up(nrp * d->hidden * s, 256) / s;
     w.feat_proj4 = take(rotv ? 4 * w.proj4_stride * s : 0);

@@ -167,7 +167,8 @@ struct Builder {
     void heads() {
         if (d->variant == DA_VARIANT_3D) {
             stacked_head0(256);
-            d->head_w1 = copy_f32(w->head_w1, 3 * 256); d->head_b1 = copy_f32(w->head_b1, 3);
+            const size_t tch = (size_t)t_channels(d);          // mlp_t.2: 3 rows, or 9 with use_6dof
+            d->head_w1 = copy_f32(w->head_w1, tch * 256); d->head_b1 = copy_f32(w->head_b1, tch);
             d->head_r_w1 = copy_f32(w->head_r_w1, 3 * 256); d->head_r_b1 = copy_f32(w->head_r_b1, 3);
         } else if (rotv) {
             stacked_head0(32);

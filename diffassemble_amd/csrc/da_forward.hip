@@ -371,7 +371,7 @@ int FwdCtx::pose_head() {
     if (disc) return 0;
     return timed(DA_PROF_HEAD, [&] {
         if (d->variant == DA_VARIANT_3D)
-            return launch_head3d(prec, nr, hh, d->head_w1, d->head_b1, d->head_r_w1, d->head_r_b1, out, pre_head, st);
+            return launch_head3d(prec, nr, t_channels(d), hh, d->head_w1, d->head_b1, d->head_r_w1, d->head_r_b1, out, pre_head, st);
         return launch_head2d(prec, nr, d->c_out, hh, d->head_w1, d->head_b1, out, st);
     });
 }
@@ -387,8 +387,18 @@ int forward_impl(da_denoiser *d, const da_graph *g, const float *x, const int64_
     if (rc) return rc;
     if (d->arch == DA_ARCH_GCN) return (rc = f.gcn_body()) ? rc : f.pose_head();
     // (a-4..a-6) graph transformer: fused Q|K|V|skip projection + attention per layer
+    // use_6dof (3D, c_in = 13): what the forward returns does not depend on whether attention weights are asked for, so the per-step
+    // sampling route (return_attentions) and the captured loop give the same bits.  Only the edge-list kernels produce the weights: a layer
+    // whose weights are wanted walks the edge list for them first -- its rows land in the layer's own destination and are overwritten --
+    // and then runs exactly as it does without the request.  (The other models keep their one pass: their outputs stay what they were.)
+    const bool alpha_apart = d->variant == DA_VARIANT_3D && d->c_in == 13;
     for (int l = 0; l < d->n_layers; ++l) {
-        const Layer ly = f.layer(l);
+        Layer ly = f.layer(l);
+        if (alpha_apart && ly.al) {
+            LayerIO unused = io;
+            if ((rc = f.edge_list_layer(ly, unused))) return rc;
+            ly.al = nullptr;
+        }
         if (ly.last && (rc = f.folded_last_layer(ly, io)) >= 0) return rc;         // taken: it ran the head behind the layer too
         if ((rc = f.conv_fused_layer(ly, io)) < 0 && (rc = f.dense_layer(ly, io)) < 0) rc = f.edge_list_layer(ly, io);
         if (rc) return rc;

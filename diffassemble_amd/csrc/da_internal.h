@@ -115,10 +115,11 @@ int launch_attn_csr(int prec, int n_nodes, const int32_t *row_ptr, const int32_t
                     float *stats /* [n, H, 2] running max and 1/(sum + 1e-16), or NULL */, hipStream_t st);
 
 // da_so3.hip (3D head + SO(3) DDIM)
-int launch_head3d(int prec, int n, const void *hh, const float *wt, const float *bt, const float *wr, const float *br,
+// t_ch = the translation head's width: 3, or 9 with use_6dof (translation | a1 | a2); pose rows are 4 + t_ch wide, [r | t] rows 3 + t_ch
+int launch_head3d(int prec, int n, int t_ch, const void *hh, const float *wt, const float *bt, const float *wr, const float *br,
                   float *out7, float *pre_head, hipStream_t st);
-int launch_head3d_bwd(int n, const float *pre, const float *d_out, float *d_pre, hipStream_t st);     // [r | t] [n, 6], d[q | t] [n, 7] -> d[r | t]
-int launch_ddim3d(const DeviceSchedule &s, int mean_type, int n, const float *x, const float *mo, const int64_t *t,
+int launch_head3d_bwd(int n, int t_ch, const float *pre, const float *d_out, float *d_pre, hipStream_t st);     // [r | t], d[q | t] -> d[r | t]
+int launch_ddim3d(const DeviceSchedule &s, int mean_type, int n, int t_ch, const float *x, const float *mo, const int64_t *t,
                   int64_t t_scalar, int ratio, int prev_all_nonneg, float *x_prev, hipStream_t st);
 
 // da_gemm_mfma.hip / da_attn_dense.hip (dense block-diagonal path)

@@ -4,6 +4,8 @@
 // (spatial_diffusion_3d_test_double_diffusion.py:595-685 with so3_scale / log_rmat of
 // utils_3d.py:1018-1061).  A few dozen flops per piece: one thread per piece, fp32.
 // Training side: the pose head's backward (k_head3d_bwd) and the SE(3) noising of p_losses (k_q_sample_se3).
+// use_6dof (13-wide pose rows: quaternion | translation | a1 | a2): the same kernels at T_CH = 9, and the Gram-Schmidt quaternion of
+// (a1, a2) that the loss and the evaluation read, with its backward (k_rot6d_to_pose, k_rot6d_to_pose_bwd).
 //
 // matrix_exp of a skew matrix is evaluated in closed form (Rodrigues); torch.matrix_exp uses
 // a scaled Taylor/Pade series -- equal to ~1e-7.  log_rmat's NaN branch (rotation by exactly
@@ -101,8 +103,10 @@ __device__ inline M3 transpose(const M3 &A) {
     return C;
 }
 
-// One wave per piece: 6 dot products of length 256 (mlp_t.2 / mlp_r.2), then lane 0 finishes.
-template <typename T>
+// One wave per piece: T_CH + 3 dot products of length 256 (mlp_t.2 / mlp_r.2), then lane 0 finishes.  T_CH = 3: the translation;
+// T_CH = 9 (use_6dof): translation | a1 | a2, the two 3-vectors the loss and the evaluation orthonormalise (k_rot6d_to_pose).
+// Rows of out are 4 + T_CH wide, rows of pre 3 + T_CH = [r | t].
+template <typename T, int T_CH>
 __global__ __launch_bounds__(256) void k_head3d(int n, const T *__restrict__ hh, const float *__restrict__ wt,
                                                 const float *__restrict__ bt, const float *__restrict__ wr,
                                                 const float *__restrict__ br, float *__restrict__ out7,
@@ -110,28 +114,42 @@ __global__ __launch_bounds__(256) void k_head3d(int n, const T *__restrict__ hh,
     const int lane = threadIdx.x & 63;
     const int r = (int)(((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     if (r >= n) return;
-    float acc[6] = {0, 0, 0, 0, 0, 0};
+    float acc[T_CH + 3];
+#pragma unroll
+    for (int c = 0; c < T_CH + 3; ++c) acc[c] = 0.f;
     const T *ht = hh + (size_t)r * 512, *hr = ht + 256;
     for (int k = lane; k < 256; k += 64) {
         const float a = ldf(ht + k), b = ldf(hr + k);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { acc[c] = fmaf(wt[c * 256 + k], a, acc[c]); acc[3 + c] = fmaf(wr[c * 256 + k], b, acc[3 + c]); }
+        for (int c = 0; c < 3; ++c) { acc[c] = fmaf(wt[c * 256 + k], a, acc[c]); acc[T_CH + c] = fmaf(wr[c * 256 + k], b, acc[T_CH + c]); }
+#pragma unroll
+        for (int c = 3; c < T_CH; ++c) acc[c] = fmaf(wt[c * 256 + k], a, acc[c]);
     }
 #pragma unroll
-    for (int c = 0; c < 6; ++c)
+    for (int c = 0; c < T_CH + 3; ++c)
         for (int o = 32; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
     if (lane != 0) return;
-    const float t0 = acc[0] + bt[0], t1 = acc[1] + bt[1], t2 = acc[2] + bt[2];
-    const float r0 = acc[3] + br[0], r1 = acc[4] + br[1], r2 = acc[5] + br[2];
-    if (pre) { float *p = pre + (size_t)r * 6; p[0] = r0; p[1] = r1; p[2] = r2; p[3] = t0; p[4] = t1; p[5] = t2; }
+    float tv[T_CH];
+#pragma unroll
+    for (int c = 0; c < T_CH; ++c) tv[c] = acc[c] + bt[c];
+    const float r0 = acc[T_CH] + br[0], r1 = acc[T_CH + 1] + br[1], r2 = acc[T_CH + 2] + br[2];
+    if (pre) {
+        float *p = pre + (size_t)r * (3 + T_CH);
+        p[0] = r0; p[1] = r1; p[2] = r2;
+#pragma unroll
+        for (int c = 0; c < T_CH; ++c) p[3 + c] = tv[c];
+    }
     float q[4];
     mat_to_quat(rodrigues(r0, r1, r2), q);
     const float nrm = fmaxf(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), 1e-12f);  // F.normalize eps
-    float *o = out7 + (size_t)r * 7;
+    float *o = out7 + (size_t)r * (4 + T_CH);
     o[0] = q[0] / nrm; o[1] = q[1] / nrm; o[2] = q[2] / nrm; o[3] = q[3] / nrm;
-    o[4] = t0; o[5] = t1; o[6] = t2;
+#pragma unroll
+    for (int c = 0; c < T_CH; ++c) o[4 + c] = tv[c];
 }
 
+// Rows of 4 + T_CH: the Gaussian DDIM update on columns 4 .. 4 + T_CH, the SO(3) update on the quaternion in columns 0 .. 3.
+template <int T_CH>
 __global__ __launch_bounds__(64) void k_ddim3d(DeviceSchedule s, int mean_type, int n, const float *__restrict__ x,
                                                const float *__restrict__ mo, const int64_t *__restrict__ t,
                                                int64_t t_scalar, int ratio, int prev_all_nonneg,
@@ -144,16 +162,19 @@ __global__ __launch_bounds__(64) void k_ddim3d(DeviceSchedule s, int mean_type, 
     const float ap = s.alphas_cumprod[ti];
     const float ap_prev = (prev_all_nonneg && tp >= 0) ? s.alphas_cumprod[tp] : 1.0f;
     const float beta = 1.0f - ap;
-    float xv[7], x0[7];
-    for (int c = 0; c < 7; ++c) {
-        xv[c] = x[(size_t)r * 7 + c];
-        const float m = mo[(size_t)r * 7 + c];
+    constexpr int W = 4 + T_CH;
+    float xv[W], x0[W];
+#pragma unroll
+    for (int c = 0; c < W; ++c) {
+        xv[c] = x[(size_t)r * W + c];
+        const float m = mo[(size_t)r * W + c];
         x0[c] = mean_type == DA_MEAN_START_X ? m : (xv[c] - sqrtf(beta) * m) / sqrtf(ap);
     }
     const float sr = s.sqrt_recip_alphas_cumprod[ti], srm1 = s.sqrt_recipm1_alphas_cumprod[ti];
     const float sq_prev = sqrtf(ap_prev), sq_dir = sqrtf(1.0f - ap_prev);
-    float *o = x_prev + (size_t)r * 7;
-    for (int c = 4; c < 7; ++c) {
+    float *o = x_prev + (size_t)r * W;
+#pragma unroll
+    for (int c = 4; c < W; ++c) {
         const float eps = (sr * xv[c] - x0[c]) / srm1;
         o[c] = sq_prev * x0[c] + sq_dir * eps;
     }
@@ -174,12 +195,15 @@ __global__ __launch_bounds__(64) void k_ddim3d(DeviceSchedule s, int mean_type, 
 // (standardize_quaternion); |q| = 1, so F.normalize contributes the tangent projection g' = g - q <q, g> and
 //   d r_j = s (-(k/2) r_j g'_w + k g'_j + m r_j <r, g'_v>),   m = (cos(th/2) / 2 - k) / th^2
 // (k -> 1/2 - th^2/48, m -> -1/24 + th^2/960 below rodrigues' th < 1e-4 switch).  One thread per piece, fp32, no atomics.
+// T_CH = 9 (use_6dof): pre [n, 12], d_out [n, 13], d_pre [n, 12]; all nine translation-head channels pass through.
+template <int T_CH>
 __global__ __launch_bounds__(64) void k_head3d_bwd(int n, const float *__restrict__ pre, const float *__restrict__ d_out,
                                                    float *__restrict__ d_pre) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float r0 = pre[(size_t)i * 6], r1 = pre[(size_t)i * 6 + 1], r2 = pre[(size_t)i * 6 + 2];
-    const float *g = d_out + (size_t)i * 7;
+    constexpr int LP = 3 + T_CH;
+    const float r0 = pre[(size_t)i * LP], r1 = pre[(size_t)i * LP + 1], r2 = pre[(size_t)i * LP + 2];
+    const float *g = d_out + (size_t)i * (4 + T_CH);
     const float th2 = r0 * r0 + r1 * r1 + r2 * r2, th = sqrtf(th2);
     float c, k, m;
     if (th < 1e-4f) {
@@ -197,11 +221,12 @@ __global__ __launch_bounds__(64) void k_head3d_bwd(int n, const float *__restric
     const float gw = g[0] - qw * dot, g1 = g[1] - q1 * dot, g2 = g[2] - q2 * dot, g3 = g[3] - q3 * dot;
     const float rg = r0 * g1 + r1 * g2 + r2 * g3;
     const float a = m * rg - 0.5f * k * gw;                 // coefficient of r_j
-    float *o = d_pre + (size_t)i * 6;
+    float *o = d_pre + (size_t)i * LP;
     o[0] = s * (k * g1 + a * r0);
     o[1] = s * (k * g2 + a * r1);
     o[2] = s * (k * g3 + a * r2);
-    o[3] = g[4]; o[4] = g[5]; o[5] = g[6];
+#pragma unroll
+    for (int c = 0; c < T_CH; ++c) o[3 + c] = g[4 + c];
 }
 
 // SE(3) noising of p_losses (spatial_diffusion_3d_test_double_diffusion.py:421-441) as one launch, one thread per piece:
@@ -219,6 +244,9 @@ __device__ __forceinline__ float igso3_loc(int k) {                // pi * linsp
     const float x = j < 500 ? step * (float)j : 1.0f - step * (float)(999 - j);
     return 3.14159265358979323846f * (x * x * x);
 }
+// SIXD (use_6dof, :424-431): x_start stays 7 wide; the Gaussian part is nine wide, [t | R0[:, 0] | R0[:, 1]] with R0 = quat_to_mat(x_start)
+// (its first two COLUMNS), noise_tr is [n, 9] and the rows written are 13 wide.  The rotation half is the same.
+template <bool SIXD>
 __global__ __launch_bounds__(64) void k_q_sample_se3(int steps, int n, const float *__restrict__ sac, const float *__restrict__ somac,
                                                      const float *__restrict__ trap, const float *__restrict__ x_start,
                                                      const int64_t *__restrict__ t, const float *__restrict__ noise_tr,
@@ -230,8 +258,18 @@ __global__ __launch_bounds__(64) void k_q_sample_se3(int steps, int n, const flo
     const int64_t ti = clampt(t[i]), t0 = clampt(t[0]);
     const float a = sac[ti], b = somac[ti];
     const float *xs = x_start + (size_t)i * 7;
-    float *o = x_noisy + (size_t)i * 7;
-    for (int c = 0; c < 3; ++c) o[4 + c] = __fadd_rn(__fmul_rn(a, xs[4 + c]), __fmul_rn(b, noise_tr[(size_t)i * 3 + c]));      // k_q_sample's expression
+    constexpr int T_CH = SIXD ? 9 : 3;
+    float *o = x_noisy + (size_t)i * (4 + T_CH);
+    const float *nz = noise_tr + (size_t)i * T_CH;
+    for (int c = 0; c < 3; ++c) o[4 + c] = __fadd_rn(__fmul_rn(a, xs[4 + c]), __fmul_rn(b, nz[c]));      // k_q_sample's expression
+    if constexpr (SIXD) {
+        const M3 R0 = quat_to_mat(xs);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {                              // columns 0 and 1 of R0
+            o[7 + c] = __fadd_rn(__fmul_rn(a, R0.m[3 * c]), __fmul_rn(b, nz[3 + c]));
+            o[10 + c] = __fadd_rn(__fmul_rn(a, R0.m[3 * c + 1]), __fmul_rn(b, nz[6 + c]));
+        }
+    }
     const float *row = trap + (size_t)ti * IGSO3_ROW, *row0 = trap + (size_t)t0 * IGSO3_ROW;
     const float u = unif[i];
     int lo = 0, hi = IGSO3_ROW;                                    // first index with row[k] > u
@@ -253,29 +291,110 @@ __global__ __launch_bounds__(64) void k_q_sample_se3(int steps, int n, const flo
     o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3];
 }
 
-int launch_head3d(int prec, int n, const void *hh, const float *wt, const float *bt, const float *wr, const float *br,
+// use_6dof: the pose the loss and the evaluation read out of a 13-wide prediction (:480-490, :826-845): translation = columns 4:7,
+// rotation = matrix_to_quaternion([b1 b2 b3]) with the Gram-Schmidt frame of a1 = columns 7:10, a2 = columns 10:13,
+//   b1 = a1 / max(|a1|, 1e-12),  u = a2 - (a2.b1) b1,  b2 = u / max(|u|, 1e-12),  b3 = b1 x b2      (the b's are the COLUMNS)
+// -> pose7 [n, 7] = [q | t].  One thread per piece, fp32, no atomics.
+struct Frame6 { float b1[3], b2[3], b3[3], n1, n2, d; };
+__device__ inline Frame6 gram_schmidt(const float *a1, const float *a2) {
+    Frame6 f;
+    f.n1 = fmaxf(sqrtf(a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2]), 1e-12f);
+    for (int c = 0; c < 3; ++c) f.b1[c] = a1[c] / f.n1;
+    f.d = a2[0] * f.b1[0] + a2[1] * f.b1[1] + a2[2] * f.b1[2];
+    float u[3];
+    for (int c = 0; c < 3; ++c) u[c] = a2[c] - f.d * f.b1[c];
+    f.n2 = fmaxf(sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), 1e-12f);
+    for (int c = 0; c < 3; ++c) f.b2[c] = u[c] / f.n2;
+    f.b3[0] = f.b1[1] * f.b2[2] - f.b1[2] * f.b2[1];
+    f.b3[1] = f.b1[2] * f.b2[0] - f.b1[0] * f.b2[2];
+    f.b3[2] = f.b1[0] * f.b2[1] - f.b1[1] * f.b2[0];
+    return f;
+}
+__device__ inline void frame_quat(const Frame6 &f, float q[4]) {
+    M3 R;
+    for (int c = 0; c < 3; ++c) { R.m[3 * c] = f.b1[c]; R.m[3 * c + 1] = f.b2[c]; R.m[3 * c + 2] = f.b3[c]; }
+    mat_to_quat(R, q);
+}
+__global__ __launch_bounds__(64) void k_rot6d_to_pose(int n, const float *__restrict__ pred, int ld, float *__restrict__ pose7) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = pred + (size_t)i * ld;
+    float a[6];
+    for (int c = 0; c < 6; ++c) a[c] = p[7 + c];
+    float q[4];
+    frame_quat(gram_schmidt(a, a + 3), q);
+    float *o = pose7 + (size_t)i * 7;
+    o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3];
+    o[4] = p[4]; o[5] = p[5]; o[6] = p[6];
+}
+
+// Its backward: d_pose7 [n, 7] = g -> d_pred [n, 13]; columns 0:4 (the head's own quaternion) get zeros, 4:7 pass through.
+// The four branches of matrix_to_quaternion are one function on SO(3), and R = [b1 b2 b3] is a rotation whatever a1, a2 are, so only
+// the differential along SO(3) matters and ONE form serves every branch.  For dR = [dw]x R the quaternion moves by
+// dq = (0, dw) (x) q / 2; with q = (w, v) as the forward returns it (the w >= 0 sign s is inside q, and constant nearby)
+//   m := dL/dw = (w g_v - g_w v + v x g_v) / 2.
+// The frame turns by dw = (b3.db2) b1 - (b3.db1) b2 + (b2.db1) b3, and with n1 = |a1|, n2 = |u|, d = a2.b1
+//   db1 = (I - b1 b1^T) da1 / n1,   b3.db2 = (b3.da2 - d b3.db1) / n2,
+// so   d a2 = (m.b1) b3 / n2,   d a1 = ((m.b3) b2 - ((m.b2) + (m.b1) d / n2) b3) / n1.
+// (Where a norm is below the 1e-12 clamp the frame is degenerate and the result is merely finite.)
+__global__ __launch_bounds__(64) void k_rot6d_to_pose_bwd(int n, const float *__restrict__ pred, int ld, const float *__restrict__ d_pose7,
+                                                          float *__restrict__ d_pred) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *p = pred + (size_t)i * ld, *g = d_pose7 + (size_t)i * 7;
+    float a[6];
+    for (int c = 0; c < 6; ++c) a[c] = p[7 + c];
+    const Frame6 f = gram_schmidt(a, a + 3);
+    float q[4];
+    frame_quat(f, q);
+    const float w = q[0], gw = g[0];
+    const float m0 = 0.5f * (w * g[1] - gw * q[1] + (q[2] * g[3] - q[3] * g[2]));
+    const float m1 = 0.5f * (w * g[2] - gw * q[2] + (q[3] * g[1] - q[1] * g[3]));
+    const float m2 = 0.5f * (w * g[3] - gw * q[3] + (q[1] * g[2] - q[2] * g[1]));
+    const float mb1 = m0 * f.b1[0] + m1 * f.b1[1] + m2 * f.b1[2];
+    const float mb2 = m0 * f.b2[0] + m1 * f.b2[1] + m2 * f.b2[2];
+    const float mb3 = m0 * f.b3[0] + m1 * f.b3[1] + m2 * f.b3[2];
+    const float k2 = mb1 / f.n2, k3 = mb2 + k2 * f.d;
+    float *o = d_pred + (size_t)i * 13;
+    o[0] = o[1] = o[2] = o[3] = 0.f;
+    o[4] = g[4]; o[5] = g[5]; o[6] = g[6];
+    for (int c = 0; c < 3; ++c) {
+        o[7 + c] = (mb3 * f.b2[c] - k3 * f.b3[c]) / f.n1;
+        o[10 + c] = k2 * f.b3[c];
+    }
+}
+
+int launch_head3d(int prec, int n, int t_ch, const void *hh, const float *wt, const float *bt, const float *wr, const float *br,
                   float *out7, float *pre_head, hipStream_t st) {
     if (n <= 0) return 0;
+    if (t_ch != 3 && t_ch != 9) { set_error("launch_head3d: t_ch %d is neither 3 nor 9", t_ch); return 2; }
     const int grid = (int)(((size_t)n * 64 + 255) / 256);
-    if (prec == DA_PREC_BF16)
-        k_head3d<bf16_t><<<grid, 256, 0, st>>>(n, (const bf16_t *)hh, wt, bt, wr, br, out7, pre_head);
-    else
-        k_head3d<float><<<grid, 256, 0, st>>>(n, (const float *)hh, wt, bt, wr, br, out7, pre_head);
+    if (prec == DA_PREC_BF16) {
+        if (t_ch == 9) k_head3d<bf16_t, 9><<<grid, 256, 0, st>>>(n, (const bf16_t *)hh, wt, bt, wr, br, out7, pre_head);
+        else k_head3d<bf16_t, 3><<<grid, 256, 0, st>>>(n, (const bf16_t *)hh, wt, bt, wr, br, out7, pre_head);
+    } else {
+        if (t_ch == 9) k_head3d<float, 9><<<grid, 256, 0, st>>>(n, (const float *)hh, wt, bt, wr, br, out7, pre_head);
+        else k_head3d<float, 3><<<grid, 256, 0, st>>>(n, (const float *)hh, wt, bt, wr, br, out7, pre_head);
+    }
     DA_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_ddim3d(const DeviceSchedule &s, int mean_type, int n, const float *x, const float *mo, const int64_t *t,
+int launch_ddim3d(const DeviceSchedule &s, int mean_type, int n, int t_ch, const float *x, const float *mo, const int64_t *t,
                   int64_t t_scalar, int ratio, int prev_all_nonneg, float *x_prev, hipStream_t st) {
     if (n <= 0) return 0;
-    k_ddim3d<<<(n + 63) / 64, 64, 0, st>>>(s, mean_type, n, x, mo, t, t_scalar, ratio, prev_all_nonneg, x_prev);
+    if (t_ch != 3 && t_ch != 9) { set_error("launch_ddim3d: t_ch %d is neither 3 nor 9", t_ch); return 2; }
+    if (t_ch == 9) k_ddim3d<9><<<(n + 63) / 64, 64, 0, st>>>(s, mean_type, n, x, mo, t, t_scalar, ratio, prev_all_nonneg, x_prev);
+    else k_ddim3d<3><<<(n + 63) / 64, 64, 0, st>>>(s, mean_type, n, x, mo, t, t_scalar, ratio, prev_all_nonneg, x_prev);
     DA_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_head3d_bwd(int n, const float *pre, const float *d_out, float *d_pre, hipStream_t st) {
+int launch_head3d_bwd(int n, int t_ch, const float *pre, const float *d_out, float *d_pre, hipStream_t st) {
     if (n <= 0) return 0;
-    k_head3d_bwd<<<(n + 63) / 64, 64, 0, st>>>(n, pre, d_out, d_pre);
+    if (t_ch != 3 && t_ch != 9) { set_error("launch_head3d_bwd: t_ch %d is neither 3 nor 9", t_ch); return 2; }
+    if (t_ch == 9) k_head3d_bwd<9><<<(n + 63) / 64, 64, 0, st>>>(n, pre, d_out, d_pre);
+    else k_head3d_bwd<3><<<(n + 63) / 64, 64, 0, st>>>(n, pre, d_out, d_pre);
     DA_LAUNCH_CHECK();
     return 0;
 }
@@ -289,7 +408,32 @@ extern "C" {
 int da_head3d_backward(int n, const float *pre, const float *d_out, float *d_pre, void *stream) {
     DA_REQUIRE(n >= 0, "da_head3d_backward: n < 0");
     DA_REQUIRE(pre && d_out && d_pre, "da_head3d_backward: null argument");
-    return launch_head3d_bwd(n, pre, d_out, d_pre, (hipStream_t)stream);
+    return launch_head3d_bwd(n, 3, pre, d_out, d_pre, (hipStream_t)stream);
+}
+
+int da_head3d_backward_ex(int n, int t_channels, const float *pre, const float *d_out, float *d_pre, void *stream) {
+    DA_REQUIRE(n >= 0, "da_head3d_backward_ex: n < 0");
+    DA_REQUIRE(t_channels == 3 || t_channels == 9, "da_head3d_backward_ex: t_channels = %d is neither 3 nor 9 (use_6dof)", t_channels);
+    DA_REQUIRE(pre && d_out && d_pre, "da_head3d_backward_ex: null argument");
+    return launch_head3d_bwd(n, t_channels, pre, d_out, d_pre, (hipStream_t)stream);
+}
+
+int da_rot6d_to_pose(int n, const float *pred, int ld, float *pose7, void *stream) {
+    DA_REQUIRE(n >= 0 && ld >= 13, "da_rot6d_to_pose: n >= 0 and ld >= 13 (got n = %d, ld = %d)", n, ld);
+    DA_REQUIRE(pred && pose7, "da_rot6d_to_pose: null argument");
+    if (n == 0) return 0;
+    k_rot6d_to_pose<<<(n + 63) / 64, 64, 0, (hipStream_t)stream>>>(n, pred, ld, pose7);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
+int da_rot6d_to_pose_backward(int n, const float *pred, int ld, const float *d_pose7, float *d_pred, void *stream) {
+    DA_REQUIRE(n >= 0 && ld >= 13, "da_rot6d_to_pose_backward: n >= 0 and ld >= 13 (got n = %d, ld = %d)", n, ld);
+    DA_REQUIRE(pred && d_pose7 && d_pred, "da_rot6d_to_pose_backward: null argument");
+    if (n == 0) return 0;
+    k_rot6d_to_pose_bwd<<<(n + 63) / 64, 64, 0, (hipStream_t)stream>>>(n, pred, ld, d_pose7, d_pred);
+    DA_LAUNCH_CHECK();
+    return 0;
 }
 
 int da_q_sample_se3(int steps, int n, const float *sqrt_alphas_cumprod, const float *sqrt_one_minus_alphas_cumprod, const float *trap,
@@ -299,8 +443,21 @@ int da_q_sample_se3(int steps, int n, const float *sqrt_alphas_cumprod, const fl
     DA_REQUIRE(sqrt_alphas_cumprod && sqrt_one_minus_alphas_cumprod && trap && x_start && t && noise_tr && axes && unif && x_noisy,
                "da_q_sample_se3: null argument");
     if (n == 0) return 0;
-    k_q_sample_se3<<<(n + 63) / 64, 64, 0, (hipStream_t)stream>>>(steps, n, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, trap, x_start, t,
-                                                                  noise_tr, axes, unif, x_noisy);
+    k_q_sample_se3<false><<<(n + 63) / 64, 64, 0, (hipStream_t)stream>>>(steps, n, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, trap, x_start, t,
+                                                                         noise_tr, axes, unif, x_noisy);
+    DA_LAUNCH_CHECK();
+    return 0;
+}
+
+int da_q_sample_se3_6d(int steps, int n, const float *sqrt_alphas_cumprod, const float *sqrt_one_minus_alphas_cumprod, const float *trap,
+                       const float *x_start, const int64_t *t, const float *noise_tr, const float *axes, const float *unif, float *x_noisy,
+                       void *stream) {
+    DA_REQUIRE(steps > 0 && n >= 0, "da_q_sample_se3_6d: steps must be positive and n >= 0");
+    DA_REQUIRE(sqrt_alphas_cumprod && sqrt_one_minus_alphas_cumprod && trap && x_start && t && noise_tr && axes && unif && x_noisy,
+               "da_q_sample_se3_6d: null argument");
+    if (n == 0) return 0;
+    k_q_sample_se3<true><<<(n + 63) / 64, 64, 0, (hipStream_t)stream>>>(steps, n, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, trap, x_start, t,
+                                                                        noise_tr, axes, unif, x_noisy);
     DA_LAUNCH_CHECK();
     return 0;
 }

@@ -128,13 +128,15 @@ static int dims_of(const da_weights *w, const da_graph *g, Dims &d, int mma = DA
         DA_REQUIRE(w->c_in == 1 && w->pos_w1, "training (discrete variant): c_in must be 1 and pos_w1 = pos_mlp.weight [K, 32]");
     }
     d.hh = d.v3d ? 512 : (d.rot ? 64 : 32);
-    DA_REQUIRE(!d.v3d || w->c_in == 7, "training (3D): c_in must be 7 (quaternion wxyz | translation), not %d", w->c_in);
-    DA_REQUIRE(w->c_in >= 1 && w->c_in <= 8, "training: c_in %d outside 1 .. 8", w->c_in);
+    DA_REQUIRE(!d.v3d || w->c_in == 7 || w->c_in == 13,
+               "training (3D): c_in must be 7 (quaternion wxyz | translation) or 13 (use_6dof: | a1 | a2), not %d", w->c_in);
+    DA_REQUIRE(d.v3d || (w->c_in >= 1 && w->c_in <= 8), "training: c_in %d outside 1 .. 8", w->c_in);
+    d.tch = d.v3d ? w->c_in - 4 : 0;
     d.gcn = w->arch == DA_ARCH_GCN;
     DA_REQUIRE(!d.gcn || w->n_layers == 2, "training: gcn arch needs n_layers = 2 (backbones/gcn.py:9-14)");
     DA_REQUIRE(w->heads == 8 && w->n_layers >= 2 && w->n_layers <= DA_MAX_LAYERS, "training: bad heads / n_layers");
     d.nr = g->n_real; d.n = g->n_nodes; d.F = w->feat_dim; d.D = w->feat_dim + 64; d.hid = w->hidden; d.H = w->heads;
-    d.L = w->n_layers; d.V = w->arch == DA_ARCH_EXOPHORMER ? w->virt_nodes : 0; d.c_in = w->c_in; d.c_out = d.v3d ? 7 : w->c_out;
+    d.L = w->n_layers; d.V = w->arch == DA_ARCH_EXOPHORMER ? w->virt_nodes : 0; d.c_in = w->c_in; d.c_out = d.v3d ? w->c_in : w->c_out;
     d.gelu_between = w->arch == DA_ARCH_TRANSFORMER || d.gcn;
     d.G = g->n_graphs;
     DA_REQUIRE(d.D % d.H == 0 && (d.D / d.H) % 8 == 0, "training: D / heads must be a multiple of 8");
@@ -231,7 +233,7 @@ static TrainWs carve_train(const Dims &d, void *base) {
     }
     w.partial2 = take(PART_CAP);
     w.dY4b = take(n * 4 * hcmax);
-    w.wt_head1 = take(d.v3d ? (size_t)3 * 256 : (size_t)d.c_out * 32);
+    w.wt_head1 = take(d.v3d ? (size_t)d.tch * 256 : (size_t)d.c_out * 32);
     w.wt_head0 = take((size_t)d.hh * d.D);
     w.wt_mlp1 = take((size_t)d.D * d.hid);
     w.wt_mlp0 = take((size_t)d.hid * d.D);
@@ -239,8 +241,8 @@ static TrainWs carve_train(const Dims &d, void *base) {
     w.wt_head_r1 = w.pre6 = w.dpre6 = nullptr;
     if (d.v3d) {
         w.wt_head_r1 = take((size_t)3 * 256);
-        w.pre6 = take(nr * 6);
-        w.dpre6 = take(nr * 6);
+        w.pre6 = take(nr * (3 + d.tch));
+        w.dpre6 = take(nr * (3 + d.tch));
     } else if (d.rot) {
         w.wt_head_r1 = take((size_t)4 * 32);
     }
@@ -288,7 +290,7 @@ static int weight_prep(const da_weights *w, const Dims &d, TrainWs &ws, hipStrea
     };
     static_assert(sizeof(WPrepTable) <= 2048, "the job table travels as a kernel argument");
     if (d.v3d) {
-        add(w->head_w1, ws.wt_head1, 3, 256, 0);
+        add(w->head_w1, ws.wt_head1, d.tch, 256, 0);
         add(w->head_r_w1, ws.wt_head_r1, 3, 256, 0);
     } else {
         add(w->head_w1, ws.wt_head1, d.c_out, 32, 0);
@@ -629,7 +631,7 @@ struct TrainCtx {
         int rc;
         if ((rc = linear_fw({.M = nr, .K = d.D, .Nout = d.hh, .A = z, .lda = d.D, .W = w->head_w0, .bias = w->head_b0, .out = ws.f1pre, .ldo = d.hh,
                              .act_out = ws.f1}))) return rc;
-        if (d.v3d) return launch_head3d(P, nr, ws.f1, w->head_w1, w->head_b1, w->head_r_w1, w->head_r_b1, out, ws.pre6, st);
+        if (d.v3d) return launch_head3d(P, nr, d.tch, ws.f1, w->head_w1, w->head_b1, w->head_r_w1, w->head_r_b1, out, ws.pre6, st);
         if (d.rot)         // Linear(32, K) over columns 0..31 and Linear(32, 4) over columns 32..63: the logits half of the rot sampling step's tail kernel
             return launch_d3pm_rot_tail(P, nr, d.c_out, ws.f1, w->head_w1, w->head_b1, w->head_r_w1, w->head_r_b1, nullptr, nullptr, out, out_rot,
                                         nullptr, st);
@@ -647,10 +649,11 @@ struct TrainCtx {
     int head3d_bwd(const float *d_out) {
         const int nr = d.nr;
         int rc;
-        if ((rc = launch_head3d_bwd(nr, ws.pre6, d_out, ws.dpre6, st))) return rc;
-        if ((rc = linear_bwd({.M = nr, .N = 3, .K = 256, .dY = ws.dpre6, .ldy = 6, .X = ws.f1 + 256, .ldx = 512, .WT = ws.wt_head_r1,
+        const int lp = 3 + d.tch;                         // [r | t] rows: 6, or 12 with use_6dof (mlp_t.2 is [9, 256] then)
+        if ((rc = launch_head3d_bwd(nr, d.tch, ws.pre6, d_out, ws.dpre6, st))) return rc;
+        if ((rc = linear_bwd({.M = nr, .N = 3, .K = 256, .dY = ws.dpre6, .ldy = lp, .X = ws.f1 + 256, .ldx = 512, .WT = ws.wt_head_r1,
                               .dW = G(grads->head_r_w1), .db = G(grads->head_r_b1), .dX = ws.df1 + 256, .lddx = 512}))) return rc;
-        if ((rc = linear_bwd({.M = nr, .N = 3, .K = 256, .dY = ws.dpre6 + 3, .ldy = 6, .X = ws.f1, .ldx = 512, .WT = ws.wt_head1,
+        if ((rc = linear_bwd({.M = nr, .N = d.tch, .K = 256, .dY = ws.dpre6 + 3, .ldy = lp, .X = ws.f1, .ldx = 512, .WT = ws.wt_head1,
                               .dW = G(grads->head_w1), .db = G(grads->head_b1), .dX = ws.df1, .lddx = 512}))) return rc;
         return gelu_bwd((size_t)nr * 512, ws.f1pre, ws.df1, ws.df1, st);
     }

@@ -162,8 +162,13 @@ class DenoiserEngine:
         if self.virt_nodes > 0:
             w.virt_emb = P("gnn_backbone.virt_node_embedding.weight")
         if variant == "3d":
-            self.c_out, self.c_pose = 6, 7
-            w.c_out = 6
+            # [r | t] head outputs and the pose row: 6 and 7, or 12 and 13 with use_6dof (mlp_t.2 is [9, 256]: translation | a1 | a2)
+            t_ch = sd["mlp_t.2.weight"].shape[0]
+            if (self.c_in, t_ch) not in ((7, 3), (13, 9)):
+                raise _lib.DaError(f"Eff_GAT_3d: input_channels = {self.c_in} with t_channels = {t_ch}; the 3D model is (7, 3), "
+                                   "or (13, 9) with use_6dof")
+            self.c_out, self.c_pose = 3 + t_ch, 4 + t_ch
+            w.c_out = self.c_out
             w.head_w0, w.head_b0 = P("mlp_t.0.weight"), P("mlp_t.0.bias")
             w.head_w1, w.head_b1 = P("mlp_t.2.weight"), P("mlp_t.2.bias")
             w.head_r_w0, w.head_r_b0 = P("mlp_r.0.weight"), P("mlp_r.0.bias")
@@ -258,7 +263,7 @@ class DenoiserEngine:
         out = torch.empty((plan.n_real, self.c_pose), dtype=torch.float32, device=self.device)
         ashape = (self.n_layers, plan.n_edges, 8) if alpha_all_layers else (plan.n_edges, 8)
         alpha = torch.empty(ashape, dtype=torch.float32, device=self.device) if return_alpha else None
-        pre = (torch.empty((plan.n_real, 6), dtype=torch.float32, device=self.device)
+        pre = (torch.empty((plan.n_real, self.c_out), dtype=torch.float32, device=self.device)
                if return_pre_head and self.variant == "3d" else None)
         if torch.is_tensor(t):
             tt, ts = t.to(device=self.device, dtype=torch.int64).contiguous(), 0

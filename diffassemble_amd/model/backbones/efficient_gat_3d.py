@@ -63,7 +63,8 @@ class Eff_GAT_3d(DenoiserBase):
         return self.forward_with_feats(xy_pos, time, edge_index, pcd_feats=self.pcd_features(pcd), batch=batch)
 
     def forward_with_feats(self, xy_pos: Tensor, time: Tensor, edge_index: Tensor, pcd_feats: Tensor, batch):
-        """efficient_gat_3d.py:173-220 -> (hstack(unit quaternion wxyz, translation) [P, 7], attentions)."""
+        """efficient_gat_3d.py:173-220 -> (hstack(unit quaternion wxyz, mlp_t's outputs) [P, 4 + t_channels], attentions): [P, 7], or
+        with ``input_channels=13, t_channels=9`` (use_6dof) [P, 13] = quaternion | translation | a1 | a2."""
         if self._wants_grad():       # training: da_train_forward now, da_train_backward under autograd (no attention weights)
             return self._run_train(xy_pos, time, edge_index, pcd_feats, batch)
         return self._run(xy_pos, time, edge_index, pcd_feats, batch, self.return_attentions)

@@ -114,7 +114,11 @@ class TrainEngine:
         self.F = self.D - 64
         self.disc = self.variant in ("discrete", "discrete_rot")
         self.c_in = 1 if self.disc else by["pos_mlp.0.weight"].shape[1]      # discrete: one position index per piece
-        self.c_out = 7 if self.variant == "3d" else by["final_mlp.2.weight"].shape[0]        # 3D: unit quaternion wxyz | translation
+        # 3D: unit quaternion wxyz | mlp_t's outputs -- the translation (7), or with use_6dof translation | a1 | a2 (13 = c_in)
+        self.c_out = 4 + by["mlp_t.2.weight"].shape[0] if self.variant == "3d" else by["final_mlp.2.weight"].shape[0]
+        if self.variant == "3d" and (self.c_in, self.c_out) not in ((7, 7), (13, 13)):
+            raise _lib.DaError(f"Eff_GAT_3d: input_channels = {self.c_in} with t_channels = {self.c_out - 4}; the 3D model is "
+                               "(7, 3), or (13, 9) with use_6dof")
         self.steps = by["time_emb.weight"].shape[0]
         self.hidden = by["mlp.0.weight"].shape[0]
         self.w = self._weights_struct(dict(zip(names, self.views)))

@@ -758,6 +758,34 @@ int da_q_sample_se3(int steps, int n, const float *sqrt_alphas_cumprod, const fl
                     const float *x_start, const int64_t *t, const float *noise_tr, const float *axes, const float *unif,
                     float *x_noisy, void *stream);
 
+/* The 3D model with use_6dof (train_3d.py --use_6dof_rot; additive to ABI 19).  A DA_VARIANT_3D denoiser with c_in = 13 is that mode:
+ * pose rows are [quaternion wxyz | translation | a1 | a2] (13 wide), mlp_t.2 (head_w1 / head_b1) is [9, 256] / [9], pos_mlp.0
+ * (pos_w0) is [16, 13]; c_out is not read.  da_denoiser_forward's out is [n_real, 13] and its pre_head [n_real, 12] = [r | t9];
+ * da_ddim_step takes c = 13 (Gaussian update on columns 4:13, SO(3) update on 0:4); the sampling loops and the training entries
+ * take and return 13-wide rows.  c_in = 7 behaves as before; any other c_in of the 3D variant is refused.
+ * In this mode da_denoiser_forward's `out` does not depend on `alpha`: a layer whose weights are requested computes them in an
+ * edge-list pass of its own and its rows by the kernels it takes without the request (the sampling loop's), so a per-step
+ * sampler that collects attention weights reproduces the captured loop bit for bit.
+ *   da_head3d_backward_ex      da_head3d_backward with the translation head's width: t_channels = 3 (the same kernel) or 9:
+ *                              pre [n, 3 + t_channels], d_out [n, 4 + t_channels] -> d_pre [n, 3 + t_channels]; every translation
+ *                              channel passes through.
+ *   da_q_sample_se3_6d         da_q_sample_se3 for the mode (:424-431): x_start stays [n, 7]; the Gaussian part is nine wide,
+ *                              [translation | R0[:, 0] | R0[:, 1]] with R0 = quaternion_to_matrix(x_start[:, :4]) (its first two
+ *                              columns); noise_tr [n, 9]; x_noisy [n, 13] = [noised quaternion | the nine noised channels].
+ *   da_rot6d_to_pose           the pose the loss and the evaluation read from a prediction (:480-490, :826-845): pred [n, ld],
+ *                              ld >= 13, columns 4:7 (translation) and 7:13 (a1 | a2) are read -> pose7 [n, 7] =
+ *                              [matrix_to_quaternion([b1 b2 b3]) | translation], b1 = a1 / max(|a1|, 1e-12), b2 = u / max(|u|, 1e-12)
+ *                              with u = a2 - (a2.b1) b1, b3 = b1 x b2 (columns).  fp32, one thread per piece.
+ *   da_rot6d_to_pose_backward  d_pose7 [n, 7] -> d_pred [n, 13] (contiguous): columns 0:4 zeros, 4:7 = d_pose7[:, 4:7], 7:13 through
+ *                              the quaternion and the Gram-Schmidt step in ONE closed form (the four branches of
+ *                              matrix_to_quaternion agree on SO(3), hence so do their differentials along it; da_so3.hip).      */
+int da_head3d_backward_ex(int n, int t_channels, const float *pre, const float *d_out, float *d_pre, void *stream);
+int da_q_sample_se3_6d(int steps, int n, const float *sqrt_alphas_cumprod, const float *sqrt_one_minus_alphas_cumprod, const float *trap,
+                       const float *x_start, const int64_t *t, const float *noise_tr, const float *axes, const float *unif,
+                       float *x_noisy, void *stream);
+int da_rot6d_to_pose(int n, const float *pred, int ld, float *pose7, void *stream);
+int da_rot6d_to_pose_backward(int n, const float *pred, int ld, const float *d_pose7, float *d_pred, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Fused Adafactor step over the flat parameter / gradient buffers (one call = one optimizer
  * step for every listed tensor, 4 launches, deterministic, no host sync).  Replaces, for the

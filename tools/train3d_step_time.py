@@ -8,7 +8,9 @@ device events on the one stream; the backward is cut at d_feats (the encoder's f
 into the encoder's own backward), so the two backward phases add up to what ``loss.backward()`` does in one piece.  `--warmup`
 whole steps first, then the mean over `--reps` steps and the spread (min .. max) of the step total.  Synthetic seeded weights /
 inputs (oracle/weights.py, tests/golden/train3d_cases.py).  One JSON line per (arch, precision).
-Run:  python tools/train3d_step_time.py [--arch transformer] [--backbone pointnet] [--reps 10] [--warmup 3] [--frozen]
+``--use-6dof``: the 13-channel model of train_3d.py --use_6dof_rot (nine Gaussian channels, da_rot6d_to_pose in front of the loss;
+its launch and its backward are counted in the ``loss`` and ``loss_denoiser_bwd`` phases).
+Run:  python tools/train3d_step_time.py [--arch transformer] [--backbone pointnet] [--reps 10] [--warmup 3] [--frozen] [--use-6dof]
 """
 import argparse
 import json
@@ -28,12 +30,21 @@ import train3d_cases as T3  # noqa: E402
 PHASES = ("noising", "encoder_fwd", "denoiser_fwd", "loss", "loss_denoiser_bwd", "encoder_bwd", "optimizer")
 
 
-def make_state(arch, D, steps=600, seed=0):
-    """T3.make_state at the denoiser width of the chosen backbone (832 with vn_dgcnn, 192 with pointnet)."""
+def make_state(arch, D, steps=600, seed=0, use_6dof=False):
+    """T3.make_state at the denoiser width of the chosen backbone (832 with vn_dgcnn, 192 with pointnet); ``use_6dof``: with the two
+    tensors the mode widens (pos_mlp.0.weight [16, 13], mlp_t.2 [9, 256] / [9])."""
     import gcn_cases as GC
     if arch == "gcn":
-        return GC.make_gcn_state(steps, 7, None, D, T3.HIDDEN, "3d", seed)
-    return W.make_denoiser_state(steps, 7, None, D=D, hidden=T3.HIDDEN, variant="3d", arch=arch, virt_nodes=T3.VIRT, seed=seed)
+        sd = GC.make_gcn_state(steps, 7, None, D, T3.HIDDEN, "3d", seed)
+    else:
+        sd = W.make_denoiser_state(steps, 7, None, D=D, hidden=T3.HIDDEN, variant="3d", arch=arch, virt_nodes=T3.VIRT, seed=seed)
+    if use_6dof:
+        g = torch.Generator().manual_seed(seed + 913)
+        sd = dict(sd)
+        sd["pos_mlp.0.weight"] = (torch.rand(16, 13, generator=g) * 2 - 1) / 13 ** 0.5
+        sd["mlp_t.2.weight"] = (torch.rand(9, 256, generator=g) * 2 - 1) / 16
+        sd["mlp_t.2.bias"] = (torch.rand(9, generator=g) * 2 - 1) / 16
+    return sd
 
 
 def one_step(m, opt, b, frozen, dev):
@@ -51,6 +62,9 @@ def one_step(m, opt, b, frozen, dev):
     ev[2].record()
     pred, _ = m.forward_with_feats(x_noisy, b["t"], b["edge_index"], pcd_feats=leaf, batch=b["batch"])
     ev[3].record()
+    if m.use_6dof:
+        from diffassemble_amd.model.spatial_diffusion_3d_test_double_diffusion import Rot6dToPoseFn
+        pred = Rot6dToPoseFn.apply(pred)
     losses = m.pose_losses(pred, b["x"], b["pts"], b["n_batch"], b["valids"])
     loss = sum(losses.values())
     ev[4].record()
@@ -75,6 +89,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--backbone", default="vn_dgcnn", choices=("vn_dgcnn", "pointnet"))
     ap.add_argument("--frozen", action="store_true", help="freeze_backbone=True: no encoder backward, FusedAdafactor alone")
+    ap.add_argument("--use-6dof", action="store_true", help="the 13-channel model (train_3d.py --use_6dof_rot)")
     args = ap.parse_args()
     from diffassemble_amd.model.spatial_diffusion_3d_test_double_diffusion import GNN_Diffusion, ModelMeanType
     assert torch.cuda.is_available(), "train3d_step_time.py measures on the GPU only"
@@ -88,8 +103,8 @@ def main():
     for arch in args.arch.split(","):
         for precision in ("fp32", "bf16"):
             m = GNN_Diffusion(steps=600, sampling="DDIM", model_mean_type=ModelMeanType.START_X, backbone=args.backbone, architecture=arch,
-                              max_num_part=n, loss_type="all", freeze_backbone=args.frozen)
-            m.model.load_state_dict(make_state(arch, m.model.gnn_feat_dim), strict=False)
+                              max_num_part=n, loss_type="all", freeze_backbone=args.frozen, use_6dof=args.use_6dof)
+            m.model.load_state_dict(make_state(arch, m.model.gnn_feat_dim, use_6dof=args.use_6dof), strict=False)
             m = m.to(dev).train()
             m.model.train_engine(dev).precision = precision
             opt = m.configure_optimizers()
@@ -100,7 +115,7 @@ def main():
             torch.cuda.synchronize(dev)
             ms = np.array([[ev[i].elapsed_time(ev[i + 1]) for i in range(len(PHASES))] for ev in runs])
             total = ms.sum(1)
-            print(json.dumps(dict(arch=arch, backbone=args.backbone, precision=precision, shapes=G, parts=n, points=args.points, pieces=P, frozen_encoder=args.frozen,
+            print(json.dumps(dict(arch=arch, backbone=args.backbone, use_6dof=args.use_6dof, precision=precision, shapes=G, parts=n, points=args.points, pieces=P, frozen_encoder=args.frozen,
                                   optimizer=type(opt).__name__, **{f"{k}_ms": round(float(v), 3) for k, v in zip(PHASES, ms.mean(0))},
                                   step_ms=round(float(total.mean()), 3), step_ms_min=round(float(total.min()), 3),
                                   step_ms_max=round(float(total.max()), 3), reps=args.reps, warmup=args.warmup)), flush=True)
