@@ -157,6 +157,13 @@ class DaPointnetTrainWeights(C.Structure):
     ]
 
 
+PNP_LAYERS = 11           # sa{1,2,3}.mlp_convs.{0,1,2}, fc1, fc2 of the PointNet++ encoder (BatchNorm folded)
+
+
+class DaPointnetPlusWeights(C.Structure):
+    _fields_ = [("w", _fp * PNP_LAYERS), ("b", _fp * PNP_LAYERS)]
+
+
 class DaPointnetTrainGrads(C.Structure):
     _fields_ = [("w", _fp * PN_LAYERS), ("gamma", _fp * PN_LAYERS), ("beta", _fp * PN_LAYERS)]
 
@@ -321,6 +328,12 @@ PROTOTYPES = {
                                             _fp, C.c_size_t, _fp]),
     "da_pointnet_train_backward": (C.c_int, [C.POINTER(DaPointnetTrainWeights), C.c_int, C.c_int, _fp, _fp, C.c_int, _fp,
                                              C.POINTER(DaPointnetTrainGrads), _fp, C.c_size_t, _fp]),
+    "da_pnp_fps": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
+    "da_pnp_ball_query": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _fp, _fp, _fp, _fp]),
+    "da_pointnet_plus_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "da_pointnet_plus_forward": (C.c_int, [C.POINTER(DaPointnetPlusWeights), C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_size_t, _fp]),
+    "da_pointnet_plus_stages": (C.c_int, [C.POINTER(DaPointnetPlusWeights), C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_size_t,
+                                          C.c_int, _fp]),
     "da_knn": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp]),
     "da_nearest_sq": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
     "da_metrics3d": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, C.c_float, _fp, _fp, _fp]),

@@ -323,8 +323,8 @@ static int launch_t(int n_nodes, const int32_t *row_ptr, const int32_t *col_src,
         return 0;
     }
     switch (C / 8) {
-        DA_CSR_CASE(1) DA_CSR_CASE(2) DA_CSR_CASE(3) DA_CSR_CASE(4) DA_CSR_CASE(8) DA_CSR_CASE(13) DA_CSR_CASE(16) DA_CSR_CASE(18)
-        default:      // (3: the 24-wide heads of the 3D model with the PointNet encoder, D = 128 + 64 = 192)
+        DA_CSR_CASE(1) DA_CSR_CASE(2) DA_CSR_CASE(3) DA_CSR_CASE(4) DA_CSR_CASE(5) DA_CSR_CASE(8) DA_CSR_CASE(13) DA_CSR_CASE(16) DA_CSR_CASE(18)
+        default:      // (3: the 24-wide heads of the 3D model with the PointNet encoder, D = 128 + 64 = 192; 5: PointNet++ / vn_dgcnn_inv, D = 320)
             set_error("da_attn_csr: unsupported head width C=%d", C);
             return 1;
     }

@@ -119,7 +119,7 @@ int launch_attn_bwd(const da_graph *g, int H, int C, const float *qkvs, const fl
         k_attn_bwd_src<E><<<grid, 256, 0, st>>>(n, g->out_ptr, g->out_dst, H, HC, qkvs, d_o, stats, Dd, dY4, scale); \
         break;
     switch (C / 8) {
-        DA_BWD_CASE(1) DA_BWD_CASE(2) DA_BWD_CASE(3) DA_BWD_CASE(4) DA_BWD_CASE(8) DA_BWD_CASE(13) DA_BWD_CASE(16) DA_BWD_CASE(18)
+        DA_BWD_CASE(1) DA_BWD_CASE(2) DA_BWD_CASE(3) DA_BWD_CASE(4) DA_BWD_CASE(5) DA_BWD_CASE(8) DA_BWD_CASE(13) DA_BWD_CASE(16) DA_BWD_CASE(18)
         default:
             set_error("attention backward: unsupported head width C=%d", C);
             return 1;

@@ -1345,6 +1345,52 @@ int da_pointnet_train_backward(const da_pointnet_train_weights *w, int n_parts, 
                                void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * PointNet++ fragment encoder (backbone="pointnet_plus"; the eval forward of the reference's PointNetPlus with
+ * normal_channel=False, backbones/pointnet.py:200-256): sa1 = 512 centres by farthest point sampling, balls of radius 0.2
+ * with 32 samples, rows [x_n - centre | x_n] through 6 -> 64 -> 64 -> 128, max per ball; sa2 = 128 centres of those 512,
+ * radius 0.4, 64 samples, rows [relative xyz | sa1 feature] through 131 -> 128 -> 128 -> 256; sa3 = all 128 points, rows
+ * [xyz | sa2 feature] through 259 -> 256 -> 512 -> 1024, max; head 1024 -> 512 -> 256.  Every layer is followed by an eval
+ * BatchNorm (folded into it by the caller) and a ReLU.  fp32 throughout, the products on v_mfma_f32_32x32x2_f32.
+ *
+ * The selection rule (discrete, hence exact): with d* = fl(p* - q*), d2(p, q) = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)).
+ * Sampling: dist[n] = 1e10, far = start; for i < npoint: idx[i] = far, dist[n] = min(dist[n], d2(x_n, x_far)), far = the
+ * lowest n attaining max dist.  Ball: the members of centre c are the n for which d2(c, x_n) > float(radius^2) is false;
+ * the first nsample of them in ascending n, the remaining slots filled with the first member.
+ * ------------------------------------------------------------------------------------- */
+enum { DA_PNP_LAYERS = 11, DA_PNP_MAX_POINTS = 2048, DA_PNP_OUT = 256 };
+typedef struct da_pointnet_plus_weights {
+    /* layer 3 s + i = sa{s+1}.mlp_convs.i with mlp_bns.i folded in; 9 = fc1 / bn1, 10 = fc2 / bn2.  w [cout][kp] row-major
+     * with the input columns in the kernels' order, zero-padded to kp: sa1.0 [rel xyz | xyz | 0 0] (kp 8); sa2.0 [feature
+     * (128) | rel xyz | 0 x 5] (kp 136); sa3.0 [feature (256) | xyz | 0 x 5] (kp 264); every other layer kp = cin. */
+    const float *w[DA_PNP_LAYERS];
+    const float *b[DA_PNP_LAYERS];           /* [cout]: folded bias (conv bias - mean) * gamma / sqrt(var + eps) + beta */
+} da_pointnet_plus_weights;
+
+/* Farthest point sampling of npoint indices out of each fragment's n_points (1 .. 2048) points [n_parts, n_points, 3];
+ * start int32 [n_parts] (clamped into range), idx int32 [n_parts, npoint].  One workgroup per fragment. */
+int da_pnp_fps(int n_parts, int n_points, int npoint, const float *points, const int32_t *start, int32_t *idx, void *stream);
+/* Ball query: centre int32 [n_parts, n_centres] = the centres' indices among the fragment's points;
+ * grp int32 [n_parts, n_centres, nsample]. */
+int da_pnp_ball_query(int n_parts, int n_points, int n_centres, int nsample, double radius, const float *points,
+                      const int32_t *centre, int32_t *grp, void *stream);
+
+/* Scratch of da_pointnet_plus_forward (indices, sa1 / sa2 features, sa3 partial maxima of at most 1024 fragments at a time). */
+size_t da_pointnet_plus_workspace_bytes(int n_parts, int n_points);
+
+/* points [n_parts, n_points, 3] fp32 -> out [n_parts, 256], row stride ld_out floats.  start1 / start2 int32 [n_parts]: the
+ * first index of sa1's sampling (among n_points) and of sa2's (among 512).  n_parts == 0 is a no-op; n_points outside
+ * 1 .. 2048 is refused.  Allocates nothing, no atomics, bitwise reproducible, a fragment's row independent of n_parts.
+ * Stream-capturable. */
+int da_pointnet_plus_forward(const da_pointnet_plus_weights *w, int n_parts, int n_points, const float *points,
+                             const int32_t *start1, const int32_t *start2, float *out, int ld_out, void *workspace,
+                             size_t workspace_bytes, void *stream);
+/* The same restricted to the stages of the bit set `stages` (1 sampling-1, 2 ball-1, 4 sa1, 8 sampling-2, 16 ball-2, 32 sa2,
+ * 64 sa3, 128 head), on the workspace an earlier full call left: for timing one stage alone. */
+int da_pointnet_plus_stages(const da_pointnet_plus_weights *w, int n_parts, int n_points, const float *points,
+                            const int32_t *start1, const int32_t *start2, float *out, int ld_out, void *workspace,
+                            size_t workspace_bytes, int stages, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Exphander graphs (dataset/puzzle_dataset.py:115-152 generate_random_regular_graph): the adjacency
  * bit rows of da_graph.mask for n_graphs graphs of n nodes and degree d, from the permutations the generator draws
  * (perms int64 [n_graphs, n]): bit j of row i of graph g = edge j -> i, rows of row_bytes bytes, graph g at
