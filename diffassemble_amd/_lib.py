@@ -164,6 +164,15 @@ class DaPointnetPlusWeights(C.Structure):
     _fields_ = [("w", _fp * PNP_LAYERS), ("b", _fp * PNP_LAYERS)]
 
 
+EFFNET_BLOCKS, EFFNET_OUT = 11, 1088       # stem + blocks.0.0 .. blocks.4.2 of the EfficientNet-B0 encoder; its output row
+EFFNET_CHUNK, EFFNET_PW_ROWS, EFFNET_PW_COLS = 0, 1, 2     # names of da_effnet_constant
+
+
+class DaEffnetWeights(C.Structure):
+    _fields_ = [("stem_w", _fp), ("stem_b", _fp)] + [
+        (k, _fp * EFFNET_BLOCKS) for k in ("exp_w", "exp_b", "dw_w", "dw_b", "se_rw", "se_rb", "se_ew", "se_eb", "prj_w", "prj_b")]
+
+
 class DaPointnetTrainGrads(C.Structure):
     _fields_ = [("w", _fp * PN_LAYERS), ("gamma", _fp * PN_LAYERS), ("beta", _fp * PN_LAYERS)]
 
@@ -334,6 +343,11 @@ PROTOTYPES = {
     "da_pointnet_plus_forward": (C.c_int, [C.POINTER(DaPointnetPlusWeights), C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_size_t, _fp]),
     "da_pointnet_plus_stages": (C.c_int, [C.POINTER(DaPointnetPlusWeights), C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_size_t,
                                           C.c_int, _fp]),
+    "da_effnet_constant": (C.c_int, [C.c_int]),
+    "da_effnet_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "da_effnet_forward": (C.c_int, [C.POINTER(DaEffnetWeights), C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_size_t, _fp]),
+    "da_effnet_forward_taps": (C.c_int, [C.POINTER(DaEffnetWeights), C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_size_t,
+                                         C.POINTER(_fp * EFFNET_BLOCKS), C.c_int, _fp]),
     "da_knn": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp]),
     "da_nearest_sq": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
     "da_metrics3d": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp, C.c_float, _fp, _fp, _fp]),

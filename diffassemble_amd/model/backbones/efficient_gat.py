@@ -6,9 +6,30 @@ import torch.nn as nn
 from torch import Tensor
 
 from ._denoiser_base import DenoiserBase, default_precision
+from .efficientnet import EfficientNetB0Features
 from .exophormer_gnn import Exophormer_GNN
 from .gcn import GCN
 from .Transformer_GNN import Transformer_GNN
+
+
+def hip_piece_encoder(model):
+    """The in-tree piece encoder ``use_hip_encoder=True`` asks for: built for ``efficientnet_b0`` only."""
+    if model != "efficientnet_b0":
+        raise NotImplementedError(f"use_hip_encoder=True with model={model!r}: the in-tree HIP encoders are efficientnet_b0 (this flag) "
+                                  "and resnet18equiv (always)")
+    return EfficientNetB0Features()
+
+
+def hip_patch_features(backbone, patch_rgb, all_equivariant=False, quarter_turns=0):
+    """``visual_features`` of the three 2D denoisers on an ``EfficientNetB0Features`` backbone: normalise + encoder + concatenation
+    of maps 2 and 3 in the HIP library, under no_grad (the encoder is frozen: its backward is not built).  ``all_equivariant``:
+    ``patch_rgb`` [N, 4, 3, 32, 32] holds four views of a piece, encoded in one batched call and averaged (efficient_gat.py:156-158)."""
+    with torch.no_grad():
+        if all_equivariant:
+            n = patch_rgb.shape[0]
+            views = patch_rgb.transpose(0, 1).reshape(4 * n, *patch_rgb.shape[2:])
+            return backbone.patch_features(views, quarter_turns).view(4, n, -1).mean(0)
+        return backbone.patch_features(patch_rgb, quarter_turns)
 
 
 class Eff_GAT(DenoiserBase):
@@ -16,14 +37,19 @@ class Eff_GAT(DenoiserBase):
 
     def __init__(self, steps, input_channels=2, output_channels=2, n_layers=4, visual_pretrained=True,
                  freeze_backbone=False, model="efficientnet_b0", architecture="transformer", virt_nodes=4,
-                 all_equivariant=False, return_attentions=True) -> None:
+                 all_equivariant=False, return_attentions=True, use_hip_encoder=False) -> None:
         super().__init__()
         # piece encoder (efficient_gat.py:37-42): NOT on the per-timestep path;
-        # built only when timm is importable, otherwise callers must pass patch_feats.
+        # built only when timm is importable, otherwise callers must pass patch_feats -- unless
+        # use_hip_encoder asks for the in-tree EfficientNet-B0 (HIP kernels, eval mode; weights from a checkpoint,
+        # visual_pretrained is not read)
+        self.use_hip_encoder = use_hip_encoder
         self.visual_backbone = None
         if model == "resnet18equiv":
             from .resnet_equivariant import ResNet18
             self.visual_backbone = ResNet18()          # P4-equivariant ResNet-18, HIP kernels (eval mode)
+        elif use_hip_encoder:
+            self.visual_backbone = hip_piece_encoder(model)
         else:
             try:
                 import timm
@@ -73,8 +99,8 @@ class Eff_GAT(DenoiserBase):
         ``model='resnet18equiv'`` (the reference's in-tree P4-equivariant ResNet-18) runs in the HIP library: eval mode
         through da_encoder_forward (BatchNorm folded), train() mode -- batch statistics, trainable unless
         ``freeze_backbone`` -- through the da_enc_* training primitives with the backward joined to autograd
-        (SURVEY 8f-2); the timm encoders are third-party and, when timm is importable, run as plain torch outside the
-        accelerated path."""
+        (SURVEY 8f-2); ``use_hip_encoder=True`` runs ``efficientnet_b0`` in the HIP library too (eval mode, frozen);
+        the timm encoders are third-party and, when timm is importable, run as plain torch outside the accelerated path."""
         if self.visual_backbone is None:
             raise NotImplementedError(
                 "no piece encoder available (timm / equivariant ResNet are outside the hot path): "
@@ -93,6 +119,8 @@ class Eff_GAT(DenoiserBase):
             else:
                 feats = self.visual_backbone.patch_features(patch_rgb)    # normalise + encoder + cat, all in HIP
             return feats.float()
+        if isinstance(self.visual_backbone, EfficientNetB0Features):      # use_hip_encoder: da_effnet_forward
+            return hip_patch_features(self.visual_backbone, patch_rgb, self.all_equivariant)
         patch_rgb = (patch_rgb - self.mean) / self.std
         if self.freeze_backbone:
             with torch.no_grad():

@@ -8,21 +8,27 @@ import torch.nn as nn
 from torch import Tensor
 
 from ._denoiser_base import DenoiserBase
+from .efficient_gat import hip_patch_features, hip_piece_encoder
+from .efficientnet import EfficientNetB0Features
 from .Transformer_GNN import Transformer_GNN
 
 
 class Eff_GAT_Discrete(DenoiserBase):
     variant = "discrete"
 
-    def __init__(self, steps, input_channels, output_channels) -> None:
+    def __init__(self, steps, input_channels, output_channels, use_hip_encoder=False) -> None:
         super().__init__()
         # piece encoder (efficient_gat_discrete.py:22-24): not on the per-timestep path; built only when timm is importable,
-        # otherwise callers pass patch_feats (as in Eff_GAT)
-        try:
-            import timm
-            self.visual_backbone = timm.create_model("efficientnet_b0", pretrained=True, features_only=True)
-        except Exception:  # noqa: BLE001  (timm absent / no weights / no network)
-            self.visual_backbone = None
+        # otherwise callers pass patch_feats (as in Eff_GAT) -- unless use_hip_encoder asks for the in-tree EfficientNet-B0
+        self.use_hip_encoder = use_hip_encoder
+        if use_hip_encoder:
+            self.visual_backbone = hip_piece_encoder("efficientnet_b0")
+        else:
+            try:
+                import timm
+                self.visual_backbone = timm.create_model("efficientnet_b0", pretrained=True, features_only=True)
+            except Exception:  # noqa: BLE001  (timm absent / no weights / no network)
+                self.visual_backbone = None
         self.input_channels, self.output_channels = input_channels, output_channels
         self.combined_features_dim = 1088 + 32 + 32
         D = self.combined_features_dim
@@ -59,6 +65,8 @@ class Eff_GAT_Discrete(DenoiserBase):
         """efficient_gat_discrete.py:99-114: normalise, piece encoder, concat feature maps 2 and 3 -> [N, 1088]."""
         if self.visual_backbone is None:
             raise NotImplementedError("no piece encoder available (timm is outside the hot path): pass precomputed patch_feats [N, 1088]")
+        if isinstance(self.visual_backbone, EfficientNetB0Features):      # use_hip_encoder: da_effnet_forward
+            return hip_patch_features(self.visual_backbone, patch_rgb)
         patch_rgb = (patch_rgb - self.mean) / self.std
         feats = self.visual_backbone.forward(patch_rgb)
         n = patch_rgb.shape[0]

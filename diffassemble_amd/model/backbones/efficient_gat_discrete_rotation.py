@@ -20,7 +20,9 @@ from torch import Tensor
 
 from ...train import DenoiserTrainFn2
 from ._denoiser_base import _Held
+from .efficient_gat import hip_patch_features
 from .efficient_gat_discrete import Eff_GAT_Discrete
+from .efficientnet import EfficientNetB0Features
 
 _NOT_BUILT = "discrete-rotation training is not built yet"
 _OFF_DEVICE = _NOT_BUILT + " off the device: it runs on ROCm tensors only (diffassemble_amd has no CPU path)"
@@ -29,12 +31,12 @@ _OFF_DEVICE = _NOT_BUILT + " off the device: it runs on ROCm tensors only (diffa
 class Eff_GAT_Discrete_ROT(Eff_GAT_Discrete):
     variant = "discrete_rot"
 
-    def __init__(self, steps=None, input_channels=None, output_channels=None, rotation_channels=4) -> None:
+    def __init__(self, steps=None, input_channels=None, output_channels=None, rotation_channels=4, use_hip_encoder=False) -> None:
         if steps is None or input_channels is None or output_channels is None:
             raise NotImplementedError("Eff_GAT_Discrete_ROT needs steps, input_channels and output_channels")
         if rotation_channels != 4:
             raise NotImplementedError("Eff_GAT_Discrete_ROT: rotation_channels must be 4 (quarter turns)")
-        super().__init__(steps, input_channels, output_channels)
+        super().__init__(steps, input_channels, output_channels, use_hip_encoder=use_hip_encoder)
         self.rotation_channels = rotation_channels
         self.final_mlp_rot = nn.Sequential(nn.Linear(self.combined_features_dim, 32), nn.GELU(), nn.Linear(32, rotation_channels))
 
@@ -80,9 +82,14 @@ class Eff_GAT_Discrete_ROT(Eff_GAT_Discrete):
 
     def visual_features4(self, patch_rgb):
         """[4, N, 1088]: image r = ``visual_features(rotate_images(patch_rgb, -r))`` (spatial_diffusion_discrete_rot.py:353, :373,
-        :542-546).  Needs the piece encoder (timm) and kornia; the table itself is the input contract of the HIP path."""
+        :542-546).  Needs the piece encoder (timm) and kornia; the table itself is the input contract of the HIP path.  On the in-tree
+        encoder (``use_hip_encoder``) no kornia: image r is the encoder reading the crops through r CLOCKWISE quarter turns --
+        ``Rotate(-90 r, mode="nearest")`` on a 32 x 32 crop is an exact quarter turn, and kornia documents positive angles as
+        counter-clockwise."""
         if self.visual_backbone is None:
             raise NotImplementedError("no piece encoder available (timm is outside the hot path): pass precomputed patch_feats [4, N, 1088]")
+        if isinstance(self.visual_backbone, EfficientNetB0Features):
+            return torch.stack([hip_patch_features(self.visual_backbone, patch_rgb, quarter_turns=r) for r in range(4)])
         try:
             from kornia.geometry.transform import Rotate
         except Exception as e:  # noqa: BLE001

@@ -132,8 +132,9 @@ class GNN_Diffusion(LightningModule):
                  input_channels=2, output_channels=2, scheduler: ModelScheduler = ModelScheduler.LINEAR,
                  visual_pretrained: bool = True, freeze_backbone: bool = True, backbone: str = "efficientnet_b0",
                  n_layers: int = 4, architecture: str = "transformer", virt_nodes: int = 4,
-                 all_equivariant=False, *args, **kwargs) -> None:
+                 all_equivariant=False, use_hip_encoder=False, *args, **kwargs) -> None:
         super().__init__(*args, **kwargs)
+        self.use_hip_encoder = use_hip_encoder      # backbone="efficientnet_b0": the in-tree HIP encoder instead of timm's (Eff_GAT)
         self.visual_pretrained = visual_pretrained
         self.free_backbone = freeze_backbone
         self.model_mean_type = model_mean_type
@@ -189,7 +190,8 @@ class GNN_Diffusion(LightningModule):
         extra = 2 if self.rotation else 0
         kw = dict(steps=self.steps, input_channels=self.input_channels + extra,
                   output_channels=self.output_channels + extra, model=self.backbone,
-                  architecture=self.architecture, n_layers=self.n_layers, virt_nodes=self.virt_nodes)
+                  architecture=self.architecture, n_layers=self.n_layers, virt_nodes=self.virt_nodes,
+                  use_hip_encoder=self.use_hip_encoder)
         if self.rotation:
             self.model = Eff_GAT(all_equivariant=self.all_equivariant, **kw)
         else:

@@ -84,7 +84,7 @@ class GNN_Diffusion(sd.GNN_Diffusion):
 
     def init_backbone(self):
         self.model = backbones.Eff_GAT_Discrete(steps=self.steps, input_channels=self.input_channels,
-                                                output_channels=self.output_channels)
+                                                output_channels=self.output_channels, use_hip_encoder=self.use_hip_encoder)
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         # a reference checkpoint carries the three [steps, K, K] transition tables; this module has their closed form instead

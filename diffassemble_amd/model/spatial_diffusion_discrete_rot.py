@@ -73,7 +73,7 @@ class GNN_Diffusion(sdd.GNN_Diffusion):
 
     def init_backbone(self):
         self.model = backbones.Eff_GAT_Discrete_ROT(steps=self.steps, input_channels=self.input_channels,
-                                                    output_channels=self.output_channels)
+                                                    output_channels=self.output_channels, use_hip_encoder=self.use_hip_encoder)
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         state_dict.pop(prefix + "overline_Q_rot", None)           # (the parent drops its own three tables)

@@ -1391,6 +1391,57 @@ int da_pointnet_plus_stages(const da_pointnet_plus_weights *w, int n_parts, int 
                             size_t workspace_bytes, int stages, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * EfficientNet-B0 piece encoder (model="efficientnet_b0", the default of the reference's train_script.py; what
+ * backbones/efficient_gat.py:149-189 keeps of timm's efficientnet_b0 under features_only=True): the eval forward of the stem
+ * (3x3 stride 2, 3 -> 32) and of blocks.0 .. blocks.4 over 32 x 32 crops, feature maps 2 (blocks.2.1: 40 x 4 x 4) and 3
+ * (blocks.4.2: 112 x 2 x 2) flattened in NCHW order into one row of 640 + 448 = 1088 values.  Every BatchNorm is eval mode,
+ * folded into the convolution in front of it by the caller; every activation is SiLU; SE(x) = x sigmoid(W_e SiLU(W_r mean_HW(x)
+ * + b_r) + b_e) on the activated depthwise output; a block with stride 1 and equal widths adds its input.  fp32 throughout.
+ *
+ * Blocks in order (input -> expansion -> output, depthwise kernel / stride, squeeze width, input size): 0 = blocks.0.0
+ * 32 -> (none) -> 16, 3 / 1, 8, 16; 1 = 1.0 16 -> 96 -> 24, 3 / 2, 4, 16; 2 = 1.1 24 -> 144 -> 24, 3 / 1, 6, 8; 3 = 2.0
+ * 24 -> 144 -> 40, 5 / 2, 6, 8; 4 = 2.1 40 -> 240 -> 40, 5 / 1, 10, 4; 5 = 3.0 40 -> 240 -> 80, 3 / 2, 10, 4; 6, 7 = 3.1, 3.2
+ * 80 -> 480 -> 80, 3 / 1, 20, 2; 8 = 4.0 80 -> 480 -> 112, 5 / 1, 20, 2; 9, 10 = 4.1, 4.2 112 -> 672 -> 112, 5 / 1, 28, 2.
+ * Below, p(c) = c rounded up to a multiple of 16 (24 -> 32, 40 -> 48); padding rows, columns and biases are ZERO.
+ * ------------------------------------------------------------------------------------- */
+enum { DA_EFFNET_BLOCKS = 11, DA_EFFNET_OUT = 1088 };
+enum { DA_EFFNET_CHUNK = 0, DA_EFFNET_PW_ROWS = 1, DA_EFFNET_PW_COLS = 2 };      /* da_effnet_constant */
+typedef struct da_effnet_weights {
+    const float *stem_w;                      /* [32][27], column c * 9 + ky * 3 + kx; bn1 folded */
+    const float *stem_b;                      /* [32] */
+    const float *exp_w[DA_EFFNET_BLOCKS];     /* conv_pw + bn1: [p(mid)][p(in)]; NULL for block 0 */
+    const float *exp_b[DA_EFFNET_BLOCKS];     /* [p(mid)] */
+    const float *dw_w[DA_EFFNET_BLOCKS];      /* conv_dw + its BatchNorm: [k * k][p(mid)], tap ky * k + kx (block 0: mid = 32) */
+    const float *dw_b[DA_EFFNET_BLOCKS];      /* [p(mid)] */
+    const float *se_rw[DA_EFFNET_BLOCKS];     /* se.conv_reduce: [r][p(mid)] */
+    const float *se_rb[DA_EFFNET_BLOCKS];     /* [r] */
+    const float *se_ew[DA_EFFNET_BLOCKS];     /* se.conv_expand TRANSPOSED: [r][p(mid)] */
+    const float *se_eb[DA_EFFNET_BLOCKS];     /* [p(mid)] */
+    const float *prj_w[DA_EFFNET_BLOCKS];     /* conv_pwl + bn3 (block 0: conv_pw + bn2): [p(out)][p(mid)] */
+    const float *prj_b[DA_EFFNET_BLOCKS];     /* [p(out)] */
+} da_effnet_weights;
+
+/* The kernels' tiling constants: DA_EFFNET_CHUNK crops per pass over the workspace, DA_EFFNET_PW_ROWS x DA_EFFNET_PW_COLS the
+ * output tile of a workgroup of the 1x1 convolutions (rows = crops * H * W).  -1 for an unknown name. */
+int da_effnet_constant(int which);
+
+/* Scratch of da_effnet_forward: the activations of at most DA_EFFNET_CHUNK crops, so it stops growing there. */
+size_t da_effnet_workspace_bytes(int n_crops);
+
+/* crops [n_crops, 3, 32, 32] fp32 in [0, 1], NOT normalised (the stem subtracts Eff_GAT's mean and divides by its std; the
+ * convolution pads the normalised image with zeros) -> out [n_crops, 1088], row stride ld_out floats.  quarter_turns 0 .. 3: the
+ * stem reads every crop turned clockwise by that many quarter turns (torch.rot90(crops, -quarter_turns, (2, 3))), bit-equal to
+ * encoding the turned crops.  n_crops == 0 is a no-op.  Allocates nothing, no atomics, bitwise reproducible, a crop's row
+ * independent of n_crops and of its position in the batch.  Stream-capturable. */
+int da_effnet_forward(const da_effnet_weights *w, int n_crops, const float *crops, int quarter_turns, float *out, int ld_out,
+                      void *workspace, size_t workspace_bytes, void *stream);
+/* The same, also writing the eleven block outputs as NCHW taps (taps: HOST array of DA_EFFNET_BLOCKS device pointers, tap b
+ * [n_crops, out_b, H_b, W_b] unpadded; NULL = none), restricted to the stages of the bit set `stages` (1 stem, 2 << b block b,
+ * 4096 the output row) on the workspace an earlier full call left: for parity per block and for timing one stage alone. */
+int da_effnet_forward_taps(const da_effnet_weights *w, int n_crops, const float *crops, int quarter_turns, float *out,
+                           int ld_out, void *workspace, size_t workspace_bytes, float *const *taps, int stages, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Exphander graphs (dataset/puzzle_dataset.py:115-152 generate_random_regular_graph): the adjacency
  * bit rows of da_graph.mask for n_graphs graphs of n nodes and degree d, from the permutations the generator draws
  * (perms int64 [n_graphs, n]): bit j of row i of graph g = edge j -> i, rows of row_bytes bytes, graph g at
