@@ -340,6 +340,7 @@ PROTOTYPES = {
     "da_pnp_fps": (C.c_int, [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
     "da_pnp_ball_query": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _fp, _fp, _fp, _fp]),
     "da_pointnet_plus_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "da_pointnet_plus_workspace_offsets": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),      # additive to ABI 19
     "da_pointnet_plus_forward": (C.c_int, [C.POINTER(DaPointnetPlusWeights), C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_size_t, _fp]),
     "da_pointnet_plus_stages": (C.c_int, [C.POINTER(DaPointnetPlusWeights), C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_size_t,
                                           C.c_int, _fp]),

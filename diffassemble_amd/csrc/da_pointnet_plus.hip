@@ -475,6 +475,15 @@ size_t da_pointnet_plus_workspace_bytes(int n_parts, int n_points) {
     return pnp_work(nullptr, n_parts < PNP_CHUNK ? n_parts : PNP_CHUNK).bytes;
 }
 
+int da_pointnet_plus_workspace_offsets(int n_parts, size_t offsets[7]) {
+    if (n_parts > 0 && offsets) {
+        const PnpWork k = pnp_work(nullptr, n_parts < PNP_CHUNK ? n_parts : PNP_CHUNK);      // base 0: the pointers ARE the offsets
+        const void *at[7] = {k.fps1, k.grp1, k.fps2, k.grp2, k.l1, k.l2, k.part};
+        for (int i = 0; i < 7; ++i) offsets[i] = (size_t)at[i];
+    }
+    return PNP_CHUNK;
+}
+
 int da_pointnet_plus_forward(const da_pointnet_plus_weights *w, int n_parts, int n_points, const float *points, const int32_t *start1,
                              const int32_t *start2, float *out, int ld_out, void *workspace, size_t workspace_bytes, void *stream) {
     if (int rc = pnp_args_ok(w, n_parts, n_points, points, start1, start2, out, ld_out, workspace, workspace_bytes, "da_pointnet_plus_forward")) return rc;

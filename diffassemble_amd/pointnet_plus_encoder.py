@@ -3,6 +3,9 @@ puzzle_diff/model/backbones/pointnet.py:200-256): packs a ``PointNetPlus`` state
 ``da_pointnet_plus_forward`` reads (include/diffassemble_hip.h) -- eval BatchNorm folded into every layer in fp64, the first
 layer of each level with its input columns in the kernels' order [features | xyz | zero padding].  No torch arithmetic on the data
 path, no CPU fallback."""
+import ctypes as C
+import math
+
 import torch
 
 from . import _lib
@@ -13,6 +16,10 @@ MAX_POINTS = 2048
 S1, S2 = 512, 128                                    # centres of sa1 / sa2
 SA_WIDTHS = ((6, 64, 64, 128), (131, 128, 128, 256), (259, 256, 512, 1024))
 STAGES = {"fps1": 1, "ball1": 2, "sa1": 4, "fps2": 8, "ball2": 16, "sa2": 32, "sa3": 64, "head": 128}
+# the workspace's stage tensors per fragment, in the order of da_pointnet_plus_workspace_offsets
+WORKSPACE_TENSORS = (("fps1", torch.int32, (512,)), ("grp1", torch.int32, (512, 32)), ("fps2", torch.int32, (128,)),
+                     ("grp2", torch.int32, (128, 64)), ("l1", torch.float32, (512, 128)), ("l2", torch.float32, (128, 256)),
+                     ("part", torch.float32, (4, 1024)))
 
 
 def _fold(w, b, sd, bn, eps):
@@ -64,6 +71,7 @@ class PointNetPlusEngine:
             l += 1
         self.w = w
         self._ws = None
+        self.chunk = int(self.lib.da_pointnet_plus_workspace_offsets(0, None))      # fragments per pass over the workspace
 
     def _put(self, w, l, wf, bf):
         wf, bf = wf.float().contiguous(), bf.float().contiguous()
@@ -109,8 +117,27 @@ class PointNetPlusEngine:
         return self._call(points, fps_start, out, None)
 
     def run_stages(self, points, fps_start, out, stages):
-        """Only the stages of the bit set (``STAGES``), on the workspace the last ``forward`` of the same shape left: for timing."""
+        """Only the stages of the bit set (``STAGES``), on the workspace the last ``forward`` of the same shape left: for timing,
+        and for tests of one stage on inputs written through ``workspace_views``."""
         return self._call(points, fps_start, out, stages)
+
+    def workspace_views(self, P):
+        """Typed views of the stage tensors in the workspace (``da_pointnet_plus_workspace_offsets``), valid after a ``forward`` /
+        ``run_stages`` of P <= ``chunk`` fragments (a larger call reuses the workspace chunk by chunk): what a stage wrote, or -- written
+        into before ``run_stages`` with one stage's bit -- what it reads.  The kernels do not bounds-check the indices: fps1 / grp1 in
+        [0, N), fps2 / grp2 in [0, 512)."""
+        P = int(P)
+        if not 1 <= P <= self.chunk:
+            raise _lib.DaError(f"PointNetPlusEngine.workspace_views: P = {P} (need 1 .. {self.chunk}, one pass over the workspace)")
+        off = (C.c_size_t * len(WORKSPACE_TENSORS))()
+        self.lib.da_pointnet_plus_workspace_offsets(P, off)
+        if self._ws is None or self._ws.numel() < self.lib.da_pointnet_plus_workspace_bytes(P, 1):
+            raise _lib.DaError(f"PointNetPlusEngine.workspace_views: no workspace of {P} fragments yet (run forward first)")
+        views = {}
+        for (name, dtype, shape), o in zip(WORKSPACE_TENSORS, off):
+            n = P * math.prod(shape)
+            views[name] = self._ws[o:o + 4 * n].view(dtype).view(P, *shape)
+        return views
 
 
 def fps(points, npoint, start):

@@ -1376,6 +1376,12 @@ int da_pnp_ball_query(int n_parts, int n_points, int n_centres, int nsample, dou
 
 /* Scratch of da_pointnet_plus_forward (indices, sa1 / sa2 features, sa3 partial maxima of at most 1024 fragments at a time). */
 size_t da_pointnet_plus_workspace_bytes(int n_parts, int n_points);
+/* Where the stage tensors of min(n_parts, chunk) fragments lie in that scratch, in bytes from its start: fps1 int32 [.,512],
+ * grp1 int32 [.,512,32], fps2 int32 [.,128] (indices among the 512), grp2 int32 [.,128,64] (likewise), l1 f32 [.,512,128],
+ * l2 f32 [.,128,256], part f32 [.,4,1024] (sa3's maxima per tile of 32 points) -- the layout the kernels use, for tests that
+ * run one stage alone.  Returns the chunk (fragments per pass over the scratch); offsets untouched when n_parts <= 0.
+ * (additive to ABI 19) */
+int da_pointnet_plus_workspace_offsets(int n_parts, size_t offsets[7]);
 
 /* points [n_parts, n_points, 3] fp32 -> out [n_parts, 256], row stride ld_out floats.  start1 / start2 int32 [n_parts]: the
  * first index of sa1's sampling (among n_points) and of sa2's (among 512).  n_parts == 0 is a no-op; n_points outside

@@ -169,7 +169,8 @@ def test_header_declares_the_functions_and_keeps_the_abi():
     from diffassemble_amd import _lib
     text = open(os.path.join(ROOT, "include", "diffassemble_hip.h")).read()
     assert re.search(r"#define\s+DA_ABI_VERSION\s+19\b", text) and _lib.ABI_VERSION == 19            # additive
-    for fn in ("da_pnp_fps", "da_pnp_ball_query", "da_pointnet_plus_workspace_bytes", "da_pointnet_plus_forward", "da_pointnet_plus_stages"):
+    for fn in ("da_pnp_fps", "da_pnp_ball_query", "da_pointnet_plus_workspace_bytes", "da_pointnet_plus_forward", "da_pointnet_plus_stages",
+               "da_pointnet_plus_workspace_offsets"):
         assert re.search(r"\b" + fn + r"\s*\(", text), fn
         assert fn in _lib.PROTOTYPES, fn
     assert os.path.exists(os.path.join(ROOT, "diffassemble_amd", "csrc", "da_pointnet_plus.hip"))
